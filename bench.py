@@ -18,10 +18,13 @@ The step is captured ONCE into a hipGraph and replayed (stp3_amd/graph.py; `--la
 from Python instead: ~1 800 dispatches and 31-39 ms of host time per step); with more than one rank the RCCL collectives of
 the step (BatchNorm statistics exchanges, gradient buckets) are captured with it.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the line (`metric`, `value`,
+`ms_per_step`, `config`, ...) and nothing else.  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (see dump_outputs).  `--full` adds every other measurement, each taken after the timed steps:
+  host_enqueue_ms_per_step  the host's own time to enqueue one step (five extra steps with the GPU drained first)
   other_workloads  (default flags on one GPU only) the reference's Prediction.yml / Planning.yml steps -- rows f2 / f3 of
                 SURVEY.md section 8 -- each measured by a child run of this file: rate, ms per step, in-run family rooflines
-                (`python bench.py --workload prediction` prints the full line of such a leg, with the reference's CPU step)
+                (`python bench.py --workload prediction --full` prints the full line of such a leg, with the reference's CPU step)
   roofline      the voxel-pool forward (stp3_lift_splat_fwd = its two kernels): algorithmic bytes per
                 launch / HIP-event time of launches on the stream they run on (measured live in this
                 process on the bench shape, right after the timed steps), against the 8 TB/s HBM3E peak;
@@ -285,11 +288,11 @@ def cpu_baseline(workload='c3', timeout_s=480.0, quick=False):
 
 def other_workload(workload, steps=10, warmup=3, timeout_s=300.0):
     """One of the widened configurations (rows f2 / f3 of SURVEY.md section 8) through a child run of this file: the captured
-    step's rate, its in-run family rooflines and host time -- the GPU side only (`bench.py --workload <w>` alone adds the
+    step's rate, its in-run family rooflines and host time -- the GPU side only (`bench.py --workload <w> --full` alone adds the
     reference's CPU step)."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), '--workload', workload, '--steps', str(steps), '--warmup', str(warmup),
-           '--no-cpu-baseline', '--no-other-workloads']
+           '--full', '--no-cpu-baseline', '--no-other-workloads']
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s)
         lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
@@ -442,6 +445,37 @@ def family_rooflines(step, batch_size, steps=3, perception_flops=True):
     return out
 
 
+DUMP_SAMPLE = 1 << 21        # elements kept of a long vector (8 MiB in float32): the files stay far below 64 MB in all
+
+
+def _sample(flat, seed):
+    """A fixed, seeded sample of a long vector (the whole vector when it is short): the same positions on every run."""
+    import numpy as np
+    n = flat.numel()
+    if n <= DUMP_SAMPLE:
+        return flat.cpu().numpy()
+    idx = np.sort(np.random.default_rng(seed).choice(n, DUMP_SAMPLE, replace=False))
+    return flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+
+
+def dump_outputs(out_dir, loss, model):
+    """What the timed path hands its caller after its last step, as DIR/<name>.npy in float32:
+      loss   the step's loss (shape [1])
+      state  the model it trained: every floating-point tensor of ``state_dict()`` (parameters after the Adam step and the
+             BatchNorm running statistics), flattened and concatenated in state_dict order
+      grads  the step's gradients, in ``parameters()`` order (a parameter without a gradient counts as zeros)
+    ``state`` and ``grads`` are ~8.8 M elements each: a fixed, seeded sample of DUMP_SAMPLE positions is written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    with torch.no_grad():
+        state = torch.cat([v.detach().reshape(-1).float() for v in model.state_dict().values() if v.is_floating_point()])
+        grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                           for p in model.parameters()])
+        arrays = {'loss': loss.detach().float().reshape(1).cpu().numpy(), 'state': _sample(state, 1), 'grads': _sample(grads, 2)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f'{name}.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def _log(msg):
     if os.environ.get('STP3_BENCH_VERBOSE'):
         print(f'[bench +{time.perf_counter() - _T0:7.1f}s] {msg}', file=sys.stderr, flush=True)
@@ -475,6 +509,13 @@ def main():
     ap.add_argument('--steps', type=int, default=100)       # ~4.5 s of timed region at N = 1
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=4, help='samples per GPU')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (loss, trained state, gradients) as '
+                         'DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure, after the timed steps: host enqueue time, family and voxel-pool '
+                         'rooflines, the CPU baseline and (c3 on one GPU) the prediction / planning legs; the --no-* options '
+                         'below leave parts of it out')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-baseline-worker', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--no-roofline', action='store_true', help='skip the voxel-pool micro-benchmark (profiling runs)')
@@ -624,28 +665,29 @@ def main():
         elapsed = max(t.item() for t in every)                 # MAX over the ranks
     _log(f'timed steps done: {elapsed / args.steps * 1e3:.2f} ms/step')
     assert DRYRUN or torch.isfinite(loss).item(), 'loss is not finite'
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, module.model)          # (before --full runs any further step)
 
-    # How long does the HOST need to enqueue one step?  With the GPU drained first, the call returns as soon as the last
-    # kernel is queued (nothing in the step reads a value back), so its duration is the host's own work per step: Python,
-    # autograd, ctypes crossings, torch dispatch.  Where it reaches ms_per_step the step is host-bound and a faster
-    # kernel buys nothing.  Five steps after the timed region; `value` is untouched.
-    host_ms = []
-    for _ in range(5):
+    host_ms = None
+    if args.full:
+        # How long does the HOST need to enqueue one step?  With the GPU drained first, the call returns as soon as the last
+        # kernel is queued (nothing in the step reads a value back), so its duration is the host's own work per step: Python,
+        # autograd, ctypes crossings, torch dispatch.  Where it reaches ms_per_step the step is host-bound and a faster
+        # kernel buys nothing.  Five steps after the timed region; `value` is untouched.
+        host_ms = []
+        for _ in range(5):
+            _sync()
+            h0 = time.perf_counter()
+            step()
+            host_ms.append((time.perf_counter() - h0) * 1e3)
         _sync()
-        h0 = time.perf_counter()
-        step()
-        host_ms.append((time.perf_counter() - h0) * 1e3)
-    _sync()
-    host_ms = sorted(host_ms)[len(host_ms) // 2]
+        host_ms = sorted(host_ms)[len(host_ms) // 2]
 
     fam = None
-    if not args.no_roofline and not DRYRUN:
+    if args.full and not args.no_roofline and not DRYRUN:
         # (per-call events need the calls: the family rooflines time the EAGER form of the same step)
         fam = family_rooflines(eager_step, args.batch, perception_flops=workload in ('c3', 'perception'))   # every rank: the steps contain the collectives
     if rank == 0:
-        module.model.prebuilt_plan = None
-        roof, kernel_ms = (None, {}) if args.no_roofline else lift_roofline(device, batch, module.model)
-        _log('roofline microbench done')
         line = {
             'metric': 'BEV samples/sec (6-cam x 3-frame fwd+bwd)' if workload in ('c3', 'perception') else
                       f'BEV samples/sec (6-cam x 3-frame + {WORKLOAD_CFG[workload]["N_FUTURE_FRAMES"]} future frames fwd+bwd, {workload} stage)',
@@ -658,33 +700,34 @@ def main():
                        'parallelism': f'dp{world}' + (' (N > 1 code path forced on one RCCL rank: --force-exchange)' if args.force_exchange else ''),
                        'launch': mode,
                        'host_options': host_options},
-            'roofline': roof,
-            'kernel_ms': kernel_ms,
             # N > 1: every rank's own clock over the same K steps (value uses the slowest), and the collectives one step
             # issues on this rank: BatchNorm statistics exchanges (forward [2C] + backward [3C] sums; sibling layers
             # share one) and gradient-bucket all-reduces
-            'host_enqueue_ms_per_step': round(host_ms, 3),
             'per_rank_ms_per_step': per_rank_ms,
             # (a replayed step issues the collectives it was captured with: counted at the capture)
             'collectives_per_step': dict(runner.collectives) if mode == 'hipgraph' else
                                     {'batchnorm_statistics_all_reduces': exchanges['batchnorm'] // max(args.steps, 1),
                                      'gradient_bucket_all_reduces': bucket_reductions // max(args.steps, 1) if buckets.exchange else 0},
-            'roofline_families': fam,
         }
-        if fam:
-            line['roofline_conv'] = fam.get('conv')
-            line['roofline_bn'] = fam.get('batchnorm')
-        if world == 1 and not args.no_cpu_baseline:
-            try:
-                # (the prediction / planning legs: B=1 at one thread count, median of 3 -- their reference step is 2-3x longer)
-                line['cpu_baseline'] = cpu_baseline(workload, quick=workload not in ('c3', 'perception'))
-            except Exception as e:  # the baseline must never take the GPU number down with it
-                line['cpu_baseline'] = {'error': repr(e)}
-        if (world == 1 and workload == 'c3' and not args.no_other_workloads and not args.no_roofline and not args.no_cpu_baseline
-                and not args.force_exchange and not DRYRUN):
-            # the reference's Prediction.yml / Planning.yml steps, each measured by a child run of
-            # this file (its own process: own model, own graph; a failure stays in its entry) -- the headline above is untouched
-            line['other_workloads'] = {w: other_workload(w) for w in ('prediction', 'planning')}
+        if args.full:
+            module.model.prebuilt_plan = None
+            roof, kernel_ms = (None, {}) if args.no_roofline else lift_roofline(device, batch, module.model)
+            _log('roofline microbench done')
+            line.update(roofline=roof, kernel_ms=kernel_ms, host_enqueue_ms_per_step=round(host_ms, 3), roofline_families=fam)
+            if fam:
+                line['roofline_conv'] = fam.get('conv')
+                line['roofline_bn'] = fam.get('batchnorm')
+            if world == 1 and not args.no_cpu_baseline:
+                try:
+                    # (the prediction / planning legs: B=1 at one thread count, median of 3 -- their reference step is 2-3x longer)
+                    line['cpu_baseline'] = cpu_baseline(workload, quick=workload not in ('c3', 'perception'))
+                except Exception as e:  # the baseline must never take the GPU number down with it
+                    line['cpu_baseline'] = {'error': repr(e)}
+            if (world == 1 and workload == 'c3' and not args.no_other_workloads and not args.no_roofline and not args.no_cpu_baseline
+                    and not args.force_exchange and not DRYRUN):
+                # the reference's Prediction.yml / Planning.yml steps, each measured by a child run
+                # of this file (its own process: own model, own graph; a failure stays in its entry) -- the headline is untouched
+                line['other_workloads'] = {w: other_workload(w) for w in ('prediction', 'planning')}
         _emit(out_fd, line)
     if world > 1:
         dist.barrier()              # rank 0 may still be in its roofline micro-benchmark: leave together

@@ -15,7 +15,7 @@ import sys
 import pandas as pd
 
 FETCH_CORRECTION = 2.0
-TOTAL_STEPS_EXTRA = 1 + 1 + 5          # bench.py --warmup 2: the set-up step, one more warm-up step, five host-enqueue steps
+TOTAL_STEPS_EXTRA = 1 + 1              # bench.py --warmup 2 (a plain run): the set-up step, one more warm-up step
 
 
 def short(name):

@@ -16,7 +16,7 @@ for setting in "$@"; do
   i=$((i + 1))
   log=$out/run_$i
   # shellcheck disable=SC2086
-  env $setting timeout 300 python bench.py --no-cpu-baseline --no-roofline --steps ${STEPS:-40} --warmup 5 \
+  env $setting timeout 300 python bench.py --full --no-cpu-baseline --no-roofline --steps ${STEPS:-40} --warmup 5 \
       ${BENCH_ARGS:-} > $log.json 2> $log.err
   rc=$?
   python - "$setting" $rc $log.json <<'PY'

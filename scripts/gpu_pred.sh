@@ -10,11 +10,11 @@ for W in "$@"; do
       timeout 900 python -m pytest tests/test_dwconv_gpu.py tests/test_prediction_gpu.py ${EXTRA_TESTS:-} -m gpu -q -x -p no:cacheprovider > $out/pytest.log 2>&1
       echo "tests rc=$?"; tail -4 $out/pytest.log | cut -c1-300 ;;
     bench)
-      timeout 600 python bench.py --workload prediction --no-cpu-baseline --no-roofline --steps ${STEPS:-20} --warmup 3 > $out/bench_prediction.json 2> $out/bench_prediction.err
+      timeout 600 python bench.py --full --workload prediction --no-cpu-baseline --no-roofline --steps ${STEPS:-20} --warmup 3 > $out/bench_prediction.json 2> $out/bench_prediction.err
       tail -2 $out/bench_prediction.err; python -c "
 import json; b=json.load(open('$out/bench_prediction.json')); print('prediction ms/step', b['ms_per_step'], 'samples/s', b['value'], b['config'].get('launch'), 'host', b.get('host_enqueue_ms_per_step'))" ;;
     planning)
-      timeout 600 python bench.py --workload planning --no-cpu-baseline --no-roofline --steps ${STEPS:-20} --warmup 3 > $out/bench_planning.json 2> $out/bench_planning.err
+      timeout 600 python bench.py --full --workload planning --no-cpu-baseline --no-roofline --steps ${STEPS:-20} --warmup 3 > $out/bench_planning.json 2> $out/bench_planning.err
       tail -2 $out/bench_planning.err; python -c "
 import json; b=json.load(open('$out/bench_planning.json')); print('planning ms/step', b['ms_per_step'], 'samples/s', b['value'], b['config'].get('launch'), 'host', b.get('host_enqueue_ms_per_step'))" ;;
     profile)

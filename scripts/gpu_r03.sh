@@ -20,7 +20,7 @@ if [ "$2" != "quick" ]; then
   timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider --deselect tests/test_step_parity_gpu.py --deselect tests/test_train_parity_gpu.py > $out/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $out/pytest.log
   tail -8 $out/pytest.log
 fi
-timeout 900 python bench.py --steps 10 --warmup 3 > $out/bench.json 2> $out/bench.err; tail -3 $out/bench.err; cat $out/bench.json
+timeout 900 python bench.py --full --steps 10 --warmup 3 > $out/bench.json 2> $out/bench.err; tail -3 $out/bench.err; cat $out/bench.json
 STEPS=4
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_r03 -o bench -- python bench.py --steps $STEPS --warmup 3 --no-cpu-baseline --no-roofline > $out/prof.log 2>&1
 grep '^{' $out/prof.log | tail -1 > $out/bench_profiled.json

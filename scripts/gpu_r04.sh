@@ -29,7 +29,7 @@ if has perftests; then
   echo "perf-change tests rc=$?"; tail -4 $out/pytest_perf.log | cut -c1-300
 fi
 if has quickbench; then
-  timeout 600 python bench.py --no-cpu-baseline > $out/bench_quick.json 2> $out/bench_quick.err; tail -3 $out/bench_quick.err
+  timeout 600 python bench.py --full --no-cpu-baseline > $out/bench_quick.json 2> $out/bench_quick.err; tail -3 $out/bench_quick.err
   python - <<PY
 import json
 b=json.load(open('$out/bench_quick.json'))
@@ -39,7 +39,7 @@ for k,v in b['roofline_families'].items():
 PY
 fi
 if has bench || has profile; then
-  if has bench; then timeout 900 python bench.py > $out/bench.json 2> $out/bench.err; tail -3 $out/bench.err; cut -c1-1500 $out/bench.json; fi
+  if has bench; then timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err; tail -3 $out/bench.err; cut -c1-1500 $out/bench.json; fi
   STEPS=4
   timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_r04 -o bench -- python bench.py --steps $STEPS --warmup 3 --no-cpu-baseline --no-roofline > $out/prof.log 2>&1
   grep '^{' $out/prof.log | tail -1 > $out/bench_profiled.json

@@ -1,7 +1,7 @@
 """CPU: bench.py's main() end to end as a dry run -- the script the driver runs on the MI355X must not fall over on
 a Python-level error.  The GPU code path runs on CPU tensors against the recording stand-in for libstp3hip.so
 (tests/model_trace.py); B=1 of the real 6-camera 224x480 x T=3 workload, one warm-up and one timed step, the
-voxel-pool roofline leg included (event timing stubbed); the cpu_baseline leg is a subprocess of the same file and
+voxel-pool roofline leg of `--full` included (event timing stubbed); the cpu_baseline leg is a subprocess of the same file and
 has its own flag.  Checks the one-line JSON contract (keys, types, the workload named after BASELINE.json)."""
 import json
 import os
@@ -25,7 +25,7 @@ def test_bench_main_dry_run(tmp_path, workload):
     env.update(STP3_BENCH_DRYRUN='1', STP3_HOST_DRYRUN='1', STP3_TRACE_LOG=str(tmp_path / 'trace.log'),
                STP3_REAL_LIB=os.path.join(PKG, 'libstp3hip.so'))
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'bench_dryrun.py'), recorder, '--steps', '1',
-                          '--warmup', '1', '--batch', '1', '--no-cpu-baseline', '--workload', workload],
+                          '--warmup', '1', '--batch', '1', '--full', '--no-cpu-baseline', '--workload', workload],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     assert 'falling back' not in out.stderr, out.stderr[-2000:]
@@ -71,6 +71,40 @@ def test_bench_main_dry_run(tmp_path, workload):
         assert entry + ' ' in trace, entry
     if workload == 'c3':                                      # the instance / flow regression losses exist in c3 only
         assert 'stp3_reg_loss_fwd ' in trace and 'stp3_reg_loss_bwd ' in trace
+
+
+@pytest.mark.skipif(shutil.which('gcc') is None, reason='needs gcc for the recording library')
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without ``--full`` the bench sets up, warms up, times ``--steps`` steps and prints the headline line: no extra step,
+    no roofline, CPU baseline or other workload.  ``--dump-outputs DIR`` writes what the last timed step computed (loss,
+    trained state, gradients) as float32 .npy files, 64 MB at most in all."""
+    import numpy as np
+    recorder = host_trace.build_recorder(str(tmp_path / 'libstp3hip_recorder.so'))
+    env = {k: v for k, v in os.environ.items() if not k.startswith('STP3_')}
+    env.update(STP3_BENCH_DRYRUN='1', STP3_HOST_DRYRUN='1', STP3_TRACE_LOG=str(tmp_path / 'trace.log'),
+               STP3_REAL_LIB=os.path.join(PKG, 'libstp3hip.so'))
+    dump = tmp_path / 'outputs'
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'bench_dryrun.py'), recorder, '--steps', '2',
+                          '--warmup', '1', '--batch', '1', '--dump-outputs', str(dump)],
+                         env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1                                        # ONE JSON line
+    line = json.loads(lines[0])
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'steps', 'warmup', 'config'):
+        assert key in line, key
+    assert line['steps'] == 2 and line['unit'] == 'samples/s' and line['higher_is_better'] is True
+    assert abs(line['value'] - 1000.0 / line['ms_per_step']) < 1e-2 * line['value'] + 1e-3
+    for key in ('roofline', 'kernel_ms', 'host_enqueue_ms_per_step', 'roofline_families', 'cpu_baseline', 'other_workloads'):
+        assert key not in line, key
+    # the set-up step (= the one warm-up step) and the two timed steps: one Adam launch each, nothing after them
+    trace = open(tmp_path / 'trace.log').read()
+    assert trace.count('stp3_optim_clip_adam ') == 3
+    assert sorted(os.listdir(dump)) == ['grads.npy', 'loss.npy', 'state.npy']
+    arrays = {f[:-4]: np.load(dump / f) for f in os.listdir(dump)}
+    assert all(a.dtype == np.float32 for a in arrays.values())
+    assert arrays['loss'].shape == (1,) and arrays['state'].ndim == 1 and arrays['grads'].ndim == 1
+    assert sum(os.path.getsize(dump / f) for f in os.listdir(dump)) <= 64 * 2 ** 20
 
 
 @pytest.mark.skipif(shutil.which('gcc') is None, reason='needs gcc for the recording library')
