@@ -788,6 +788,35 @@ int stp3_traj_cost_bwd(const stp3_plan_dims* dims, const float* grad_cost_fo, co
                        const float* cv_scale, float* grad_cost_volume, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Planner: the candidate set (csrc/stp3_sampler.hip) -- the reference's trajectory sampler, stp3/utils/sampler.py:8-146, as
+ * its loaders call it (stp3/datas/NuscenesData.py:389-437: T0 = (0, 1), N0 = (1, 0) for kappa <= 0 else (-1, 0), frames
+ * dt = 0.5 s apart, [:, ::10]): M trajectories per sample -- straight lines (:47-49), arcs about the curvature clamped to
+ * |kappa| >= 0.01 (:53-66) and clothoids through the Fresnel integrals (:72-104) around the measured speed (:28-37), one
+ * curve block mirrored depending on the sign of kappa (:129-140) -- evaluated at the n_future + 1 frame times only, ordered by
+ * the lateral position of the last pose (:143-144).  One launch per batch, one workgroup per sample, nothing allocated.
+ *   v0, kappa  [B] float64              initial speed (m/s), curvature (1/m, positive: left)
+ *   draws      [B][3 M + 2 Mc] float64  uniforms in [0, 1), Mc = n_left + n_right, in the order the reference consumes its
+ *                                       random stream: accelerations [M], velocity candidates [M], velocity selection [M]
+ *                                       (< 0.2 keeps v0), clothoid scales [Mc], arc-or-clothoid pick [Mc] (< 0.2: arc)
+ *   trajs      [B][M][n_future + 1][3] float32  (x lateral, y forward, heading); float64 arithmetic, rounded on the store
+ *   order      [B][M] int32, optional (NULL): the generation index of each output row -- its row in the reference's array
+ *                                       before the sort, [left | lines | right] (:142)
+ *   sort != 0: rows in ascending order of the STORED (float32) x of the last pose, equal keys in ascending generation index
+ *              (the reference's argsort is not stable and its straight lines all tie at 0); sort == 0: generation order.
+ * STP3_EINVAL: B, M or n_future < 1, a negative count, n_left + n_straight + n_right != M, dt <= 0, a null pointer (order
+ * excepted).  Limit: M <= 8 192 (the keys of a sample, 8 bytes each, in 64 KB of one workgroup's LDS); else STP3_EUNSUP.
+ * Both are answered before anything touches the GPU. */
+typedef struct stp3_sampler_dims {
+    int32_t B, M;
+    int32_t n_left, n_straight, n_right;          /* int(M p) of the reference's possibility = (0.4, 0.2, 0.4), :24-26 */
+    int32_t n_future;
+    double dt;                                    /* 0.5 s */
+    int32_t sort;
+} stp3_sampler_dims;
+int stp3_traj_sample(const stp3_sampler_dims* dims, const double* v0, const double* kappa, const double* draws,
+                     float* trajs, int32_t* order, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Camera images: decoded bytes -> network input (csrc/stp3_image.hip).  The per-image chain of the reference's loader,
  * stp3/datas/NuscenesData.py:236-244: resize_and_crop_image (stp3/utils/geometry.py:9-13: PIL resize BILINEAR + crop)
  * followed by torchvision ToTensor + Normalize (:68-72), for all N images of a batch in one launch.

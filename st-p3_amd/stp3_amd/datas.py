@@ -395,6 +395,32 @@ def instance_labels(instance, future_egomotion, num_instances, ignore_index=255,
     return center, offset, flow
 
 
+WHEEL_BASE = 2.588                                  # metres between the axles (NuscenesData.py:425)
+
+
+def trajectory_curvature(steering, left_hand_traffic=False):
+    """Curvature (1/m, positive: left) from the CAN bus' steering-angle feedback (rad), float64 (B,):
+    ``Kappa = 2 * steering / 2.588``, the steering negated where the map drives on the left (singapore-*),
+    NuscenesData.py:418-425.  ``left_hand_traffic``: one flag, or one per sample."""
+    steering = torch.as_tensor(steering).double().reshape(-1)
+    flip = torch.as_tensor(left_hand_traffic, device=steering.device).bool().reshape(-1).expand_as(steering)
+    return 2.0 * torch.where(flip, steering * -1.0, steering) / WHEEL_BASE
+
+
+def trajectory_sampling(speed, steering, n_future, sample_num, left_hand_traffic=False, draws=None, generator=None,
+                        possibility=(0.4, 0.2, 0.4)):
+    """``NuscenesData.get_trajectory_sampling`` (NuscenesData.py:389-437) after its CAN-bus lookup, for a batch: ``speed``
+    (m/s, the pose message's longitudinal velocity) and ``steering`` (rad) tensors (B,) -> the batch's ``sample_trajectory``
+    entry, (B, sample_num, n_future + 1, 3) float32 on the inputs' device, ordered by the lateral position of the last
+    pose as ``Planning.command_samples`` expects it.  One launch of ``stp3_traj_sample`` for GPU tensors
+    (``ops_plan.sample_trajectories``, which documents ``draws`` / ``generator``)."""
+    from . import ops_plan
+    speed = torch.as_tensor(speed)
+    kappa = trajectory_curvature(torch.as_tensor(steering, device=speed.device), left_hand_traffic)
+    return ops_plan.sample_trajectories(speed, kappa, n_future, sample_num, draws=draws, generator=generator,
+                                        possibility=possibility)
+
+
 SAMPLE_CAT_KEYS = ('image', 'intrinsics', 'extrinsics', 'depths', 'segmentation', 'instance', 'future_egomotion', 'hdmap',
                    'pedestrian')
 
