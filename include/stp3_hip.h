@@ -817,6 +817,53 @@ int stp3_traj_sample(const stp3_sampler_dims* dims, const double* v0, const doub
                      float* trajs, int32_t* order, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Vehicle instances from the centerness / offset / flow heads (csrc/stp3_instance.hip) -- the reference's post-processing,
+ * stp3/utils/instance.py:80-269, as its validation step and evaluate.py call it (predict_instance_segmentation_and_
+ * trajectories, :272-306).  The same rules as torch code: st-p3_amd/stp3_amd/instance.py.
+ *
+ * stp3_instance_segment -- get_instance_segmentation_and_centers (:116-144: find_instance_centers :80-91, group_pixels
+ * :94-113, make_instance_seg_consecutive :165-170) for N = B * S frames in one launch, one workgroup per frame.
+ *   center      [N][H][W] float32      centerness
+ *   offset      [N][2][H][W] float32   (row, column) offset to the instance centre
+ *   foreground  [N][H][W] uint8        non-zero: the pixel's class is the vehicle class
+ *   seg         [N][H][W] int32        instance ids
+ *   centers     [N][100][2] int32      (row, column) of the centres, zero beyond counts[n]
+ *   counts      [N] int32
+ *   - a centre: t = (x <= conf_threshold ? -1 : x) is > 0 and equals the maximum of t over the 3x3 neighbourhood inside the
+ *     image; every tied pixel of a plateau is one; a NaN in the neighbourhood disqualifies (max_pool2d propagates it);
+ *   - centres are numbered in row-major order and cut to the first 100 (max_n_instance_centers);
+ *   - a pixel's centre: the k with the lowest float32 sqrt(dr * dr + dc * dc), dr = row_k - (row + offset[0]), without
+ *     contraction and with a correctly rounded square root, the lowest k on equal values;
+ *   - id = (k + 1) * (foreground != 0), then replaced by its rank among the distinct ids of the frame -- a frame without a
+ *     background pixel has no id 0, so its lowest id becomes 0 (the reference's behaviour);
+ *   - a frame without centres: all ids 0, count 0 (:130-132).
+ *
+ * stp3_instance_track -- make_instance_id_temporally_consistent (:173-269) for B samples in one launch, one workgroup per
+ * sample, the loop over the S frames inside.
+ *   raw    [B][S][H][W] int32      ids of stp3_instance_segment: per frame 0..n, every value present, n <= 100
+ *   flow   [B][S][2][H][W] float32 (row, column) displacement to the next frame; NULL: zero flow
+ *   out    [B][S][H][W] int32      consistent ids; frame 0 is raw frame 0
+ *   err    [4] int32, zeroed by the caller: word k is set to 1 when  0: the assignment hit its iteration bound,  1: a raw
+ *          frame's ids are not 0..n <= 100 with every value present (an offending pixel counts as background),  2: a frame
+ *          has no background pixel,  3: a flow value of an instance pixel is not finite or >= 32768 in magnitude (taken as
+ *          0).  The kernel always runs to its end.
+ *   Per step t: rows = the ids of the consistent frame t, ascending, at the mean of (row, col) + flow[t] over their pixels;
+ *   columns = ids 1..n of raw frame t + 1 at their pixel means; means are exact sums (integer coordinates, flow rounded to
+ *   2^-20 pixel) divided in float64 and rounded to float32; float32 Euclidean distances; minimum-cost assignment by
+ *   shortest augmenting paths over the smaller side in float64 (the method of scipy's linear_sum_assignment, its tie rule
+ *   included); pairs with distance < matching_threshold keep the row's id; every other id of frame t + 1 gets
+ *   ++largest_instance_id IN ASCENDING ORDER OF ITS OLD ID (the reference hands them out in the iteration order of a Python
+ *   set, :257-264, which is not an order: results agree up to a renaming of ids created at the same step).  No instance at t
+ *   or none at t + 1: the raw frame is taken over (:211-214, :228-231); largest_instance_id starts at the maximum of frame
+ *   0 and is carried across.
+ * Both: STP3_EINVAL for a count or side < 1 or a null pointer (flow excepted); STP3_EUNSUP for H or W > 1024 or
+ * H * W >= 2^24.  Answered before anything touches the GPU. */
+int stp3_instance_segment(int32_t N, int32_t H, int32_t W, float conf_threshold, const float* center, const float* offset,
+                          const uint8_t* foreground, int32_t* seg, int32_t* centers, int32_t* counts, void* stream);
+int stp3_instance_track(int32_t B, int32_t S, int32_t H, int32_t W, float matching_threshold, const int32_t* raw,
+                        const float* flow, int32_t* out, int32_t* err, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Camera images: decoded bytes -> network input (csrc/stp3_image.hip).  The per-image chain of the reference's loader,
  * stp3/datas/NuscenesData.py:236-244: resize_and_crop_image (stp3/utils/geometry.py:9-13: PIL resize BILINEAR + crop)
  * followed by torchvision ToTensor + Normalize (:68-72), for all N images of a batch in one launch.

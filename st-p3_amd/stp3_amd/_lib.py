@@ -262,6 +262,8 @@ SIGNATURES = {
     'stp3_traj_cost_fwd': (c_int, [ctypes.POINTER(PlanDims)] + [c_void_p] * 14),
     'stp3_traj_cost_bwd': (c_int, [ctypes.POINTER(PlanDims)] + [c_void_p] * 5),
     'stp3_traj_sample': (c_int, [ctypes.POINTER(SamplerDims)] + [c_void_p] * 6),
+    'stp3_instance_segment': (c_int, [c_int32] * 3 + [c_float] + [c_void_p] * 7),
+    'stp3_instance_track': (c_int, [c_int32] * 4 + [c_float] + [c_void_p] * 5),
     'stp3_image_prep_rows_per_workgroup': (c_int, []),
     'stp3_image_prep_lds_bytes': (c_int, [ctypes.POINTER(ImageDims), c_int32, ctypes.POINTER(c_size_t)]),
     'stp3_image_prep': (c_int, [ctypes.POINTER(ImageDims)] + [c_void_p] * 5 + [c_int32, c_void_p, c_void_p]),

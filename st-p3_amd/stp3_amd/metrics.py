@@ -3,6 +3,7 @@ tp / fp / fn accumulated over batches, IoU = tp / (tp + fp + fn), ``absent_score
 has neither support nor predictions).  The reference builds on pytorch-lightning's ``Metric`` /
 ``stat_scores_multiple_classes`` (not installed); states are plain buffers here and ``sync()``
 sums them over the process group (``dist_reduce_fx='sum'``)."""
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -128,3 +129,111 @@ class PlanningMetric(nn.Module):
 
     def compute(self):
         return {'obj_col': self.obj_col / self.total, 'obj_box_col': self.obj_box_col / self.total, 'L2': self.L2 / self.total}
+
+
+class PanopticMetric(nn.Module):
+    """Panoptic quality of the vehicle instances (``stp3/metrics.py:74-261``): per class ``iou`` (summed IoU of the matched
+    segments), ``true_positive``, ``false_positive``, ``false_negative``; ``compute()`` -> pq / sq / rq.  Inputs as the
+    reference's: predicted (temporally consistent) and ground-truth instance ids (B, S, H, W), 0 = background; the semantic
+    map is ``ids > 0``, so background is class 0 and every instance class 1.
+
+    The overlap counts of ALL frames of an update come from one table: the distinct (frame, ground-truth id, predicted id)
+    triples with their pixel counts (``torch.unique`` on packed keys, where the reference bincounts an (n + 3)^2 confusion
+    matrix per frame) -- a few hundred rows, copied to the host once.  What is sequential runs on that table
+    (``frame_results``): segments with IoU > 0.5 and the same class are matched (:188-194); a matched vehicle whose
+    ground-truth id was last matched to ANOTHER predicted id counts as a false negative plus a false positive instead
+    (:201-207); a ground-truth / predicted segment is a false negative / positive if it has pixels and no class-matching
+    IoU > 0.5 partner, rejected partners included (:213-227).  IoUs are evaluated and summed in float32 in the reference's
+    order (ground-truth id, then predicted id, background first), so one ``update`` on a fresh metric gives its bits."""
+    KEYS = ('iou', 'true_positive', 'false_positive', 'false_negative')
+    ID_BITS = 20                                  # ids < 2^20, frames < 2^23 in the packed int64 key
+
+    def __init__(self, n_classes, temporally_consistent=True, vehicles_id=1):
+        super().__init__()
+        assert n_classes >= 2
+        self.n_classes, self.temporally_consistent, self.vehicles_id = n_classes, temporally_consistent, vehicles_id
+        for name in self.KEYS:
+            self.register_buffer(name, torch.zeros(n_classes), persistent=False)
+
+    def reset(self):
+        for name in self.KEYS:
+            getattr(self, name).zero_()
+
+    def overlap_table(self, pred_instance, gt_instance):
+        """int64 numpy (rows, 4): frame, ground-truth id, predicted id, pixels -- sorted; one device-to-host copy."""
+        assert pred_instance.shape == gt_instance.shape and gt_instance.dim() == 4
+        b, s, h, w = gt_instance.shape
+        pred, gt = pred_instance.detach().long().reshape(b * s, -1), gt_instance.detach().long().reshape(b * s, -1)
+        frame = torch.arange(b * s, device=gt.device).view(-1, 1)
+        keys, counts = torch.unique((frame << (2 * self.ID_BITS)) | (gt << self.ID_BITS) | pred, return_counts=True)
+        table = torch.stack([keys, counts]).cpu().numpy()
+        mask = (1 << self.ID_BITS) - 1
+        k = table[0]
+        out = np.stack([k >> (2 * self.ID_BITS), (k >> self.ID_BITS) & mask, k & mask, table[1]], axis=1)
+        if not (out[:, 1:3] >= 0).all() or (out[:, 0] >= b * s).any():
+            raise ValueError('instance ids must lie in [0, 2^20)')
+        assert (out[:, 1] == 0).any(), 'ID 0 of gt_instance must be background'
+        return out
+
+    def frame_results(self, table, batch_size, sequence_length):
+        """float32 numpy (B * S, 4, n_classes): the reference's ``panoptic_metrics`` result of every frame, in update order."""
+        one, eps, half = np.float32(1.0), np.float32(1e-9), np.float32(0.5)
+        results = np.zeros((batch_size * sequence_length, 4, self.n_classes), np.float32)
+        starts = np.searchsorted(table[:, 0], np.arange(batch_size * sequence_length + 1))
+        for b in range(batch_size):
+            last_match = {}                       # unique_id_mapping: ground-truth id -> predicted id of its last match
+            for t in range(sequence_length):
+                f = b * sequence_length + t
+                rows = table[starts[f]:starts[f + 1]]
+                res = results[f]
+                area_g, area_p = {}, {}
+                for _, g, p, n in rows:
+                    area_g[g] = area_g.get(g, 0) + n
+                    area_p[p] = area_p.get(p, 0) + n
+                matched_g, matched_p = set(), set()
+                for _, g, p, n in rows:           # sorted by (g, p): the order of (iou > 0.5).nonzero()
+                    iou = (np.float32(n) + eps) / (np.float32(area_g[g] + area_p[p] - n) + eps)
+                    if not iou > half or (g == 0) != (p == 0):
+                        continue
+                    matched_g.add(g)
+                    matched_p.add(p)
+                    cls = 0 if g == 0 else 1
+                    if self.temporally_consistent and cls == self.vehicles_id and last_match.get(g, p) != p:
+                        res[3, cls] += one
+                        res[2, cls] += one
+                        last_match[g] = p
+                        continue
+                    res[1, cls] += one
+                    res[0, cls] += iou
+                    last_match[g] = p
+                res[3, 1] += np.float32(sum(1 for g in area_g if g > 0 and g not in matched_g))
+                res[2, 1] += np.float32(sum(1 for p in area_p if p > 0 and p not in matched_p))
+        return results
+
+    @torch.no_grad()
+    def update(self, pred_instance, gt_instance):
+        """pred_instance, gt_instance (B, S, H, W) integer ids."""
+        b, s = gt_instance.shape[:2]
+        results = self.frame_results(self.overlap_table(pred_instance, gt_instance), b, s)
+        total = np.zeros((4, self.n_classes), np.float32)
+        for r in results:                         # frame by frame, as the reference adds them to its states
+            total += r
+        total = torch.from_numpy(total).to(self.iou.device)
+        for i, name in enumerate(self.KEYS):
+            getattr(self, name).add_(total[i])
+
+    def forward(self, pred_instance, gt_instance):
+        self.update(pred_instance, gt_instance)
+
+    def sync(self, group=None):
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            packed = torch.stack([getattr(self, name) for name in self.KEYS])
+            dist.all_reduce(packed, group=group)
+            self.iou, self.true_positive, self.false_positive, self.false_negative = packed.unbind(0)
+
+    def compute(self):
+        ones = torch.ones_like(self.true_positive)
+        denominator = torch.maximum(self.true_positive + self.false_positive / 2 + self.false_negative / 2, ones)
+        return {'pq': self.iou / denominator, 'sq': self.iou / torch.maximum(self.true_positive, ones),
+                'rq': self.true_positive / denominator}

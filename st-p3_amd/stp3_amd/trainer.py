@@ -17,7 +17,7 @@ from .config import get_cfg
 from .geometry import (cumulative_warp_features, cumulative_warp_features_reverse, label_warp_thetas,
                        warp_with_theta)
 from .losses import DepthLoss, HDmapLoss, SegmentationLoss, SpatialRegressionLoss
-from .metrics import IntersectionOverUnion, PlanningMetric
+from .metrics import IntersectionOverUnion, PanopticMetric, PlanningMetric
 from .models.stp3 import STP3
 
 
@@ -82,6 +82,7 @@ class TrainingModule(nn.Module):
                 norm=1, future_discount=cfg.FUTURE_DISCOUNT, ignore_index=cfg.DATASET.IGNORE_INDEX)
             self.model.centerness_weight = _scalar()
             self.model.offset_weight = _scalar()
+            self.metric_panoptic_val = PanopticMetric(n_classes=self.n_classes)
         if cfg.INSTANCE_FLOW.ENABLED:
             self.losses_fn['instance_flow'] = SpatialRegressionLoss(
                 norm=1, future_discount=cfg.FUTURE_DISCOUNT, ignore_index=cfg.DATASET.IGNORE_INDEX)
@@ -166,6 +167,11 @@ class TrainingModule(nn.Module):
                 for i in range(len(self.hdmap_class)):
                     hd_pred = torch.argmax(output['hdmap'][:, 2 * i:2 * (i + 1)].detach(), dim=1, keepdim=True)
                     self.metric_hdmap_val[i](hd_pred, labels['hdmap'][:, i:i + 1])
+            if cfg.INSTANCE_SEG.ENABLED:
+                # trainer.py:222-228: all S frames are post-processed, the present frame onwards is scored
+                from .instance import predict_instance_segmentation_and_trajectories
+                consistent = predict_instance_segmentation_and_trajectories(output, compute_matched_centers=False)
+                self.metric_panoptic_val(consistent[:, rf - 1:], labels['instance'][:, rf - 1:])
             final_traj = None
             if cfg.PLANNING.ENABLED:
                 # trainer.py:230-246: predicted occupancy and hd map steer the planner, the labels judge the result
