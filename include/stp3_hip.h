@@ -939,6 +939,56 @@ int stp3_instance_labels(int32_t T, int32_t H, int32_t W, int32_t K, float ignor
                          const int64_t* instance, const float* warped, void* workspace, size_t workspace_bytes,
                          float* center, float* offset, float* flow, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Inference: convolution -> eval BatchNorm -> activation (+ skip) in ONE pass over the layer's tensor (csrc/stp3_conv.hip,
+ * csrc/stp3_dwconv.hip, csrc/stp3_bnact.hip).  What they serve: the eval forward the reference runs per validation sample
+ * (evaluate.py:88-91) and per simulator tick -- stp3/models/stp3.py:132-184 (forward), encoder.py:57-97 (EfficientNet
+ * trunk + heads), decoder.py:91-140 (ResNet-18 BEV decoder + heads) -- with every BatchNorm on its running statistics.
+ * The stored route is  stp3_conv2d_fwd / stp3_dwconv2d_fwd  (bf16 tensor written)  then  stp3_bn_apply_fwd  in eval mode
+ * (tensor read back, written again); the entry points below KEEP ITS ROUNDING POINTS -- the float32 accumulator (+ bias) is
+ * rounded to bf16, then  t = fma(v, scale, shift);  [t += res];  t = act(t);  [t += res]  in float32 as the eval branch of
+ * stp3_bn_apply_fwd evaluates it, one rounding at the end -- so their results are BIT-EQUAL to the two operators'.
+ *
+ * stp3_bn_eval_coefs -- the per-channel constants of every eval BatchNorm of a model, one table-driven launch (as
+ *   stp3_conv2d_prep_weights): entry e writes  out[0 .. lanes) = scale, out[lanes .. 2 lanes) = shift  with
+ *   invstd = 1 / sqrt(running_var + eps), scale = gamma * invstd, shift = beta - running_mean * scale  (gamma / beta NULL: 1 /
+ *   0) -- the device expression of stp3_bn_apply_fwd's eval branch -- and ZERO in the lanes [channels, lanes) (zero-padded
+ *   channel lanes: 35 channels in 40 lanes).  first_block: exclusive scan of ceil(lanes / 256) over the entries.
+ * stp3_conv2d_fwd_affine -- stp3_conv2d_fwd (same kernels, same tiles, same accumulation order for the same dims) with that
+ *   epilogue.  coef = [scale | shift][Cout] float32; channels <= Cout = the BatchNorm's channel count, Cout = channels
+ *   rounded up to 8 (the lanes beyond are written as zeros); res NULL or [N][Ho][Wo][ldres] bf16 added before or after
+ *   the activation (res_mode STP3_RES_*); y [N][Ho][Wo][ldy] bf16 with ldy >= Cout (a channel slice of a wider tensor).
+ *   sbias NULL or [N][channels] float32, a per-sample bias in front of the BatchNorm (the folded image-pooling branch of an
+ *   ASPP projection): shift = fma(sbias, scale, shift) per sample, as stp3_bn_apply_fwd folds it; taken by the tiled kernel
+ *   only (layers the streaming pointwise kernels run -- 1x1, Cin <= 128, Cout >= 64 -- answer STP3_EUNSUP with an sbias).
+ *   STP3_EUNSUP unless: bf16 output, Cout / ldy / ldres multiples of 8, y / res 16-byte aligned.
+ * stp3_dwconv2d_fwd_affine -- stp3_dwconv2d_fwd (bf16; 3x3 / 5x5, stride 1 / 2) with the same epilogue, no skip:
+ *   coef = [scale | shift][C].
+ * stp3_linear_fwd_affine -- stp3_linear_fwd with the eval BatchNorm + activation of a pooled descriptor (ASPP image pooling,
+ *   stp3/layers/convolutions.py:229-240) applied to the float32 value it would have stored: scale = coef[n],
+ *   shift = coef[ldcoef + n].
+ */
+typedef struct stp3_bn_coef_entry {
+    const float* running_mean;  /* [channels] */
+    const float* running_var;
+    const float* gamma;         /* NULL: 1 */
+    const float* beta;          /* NULL: 0 */
+    float* out;                 /* [2][lanes] */
+    int64_t first_block;
+    int32_t channels, lanes;
+    float eps;
+    int32_t reserved;
+} stp3_bn_coef_entry;
+
+int stp3_bn_eval_coefs(const stp3_bn_coef_entry* table, int32_t n_entries, int64_t total_blocks, void* stream);
+int stp3_conv2d_fwd_affine(const stp3_conv_dims* dims, const void* x, const void* w, const float* bias, const float* coef,
+                           const float* sbias, int32_t channels, int32_t act, const void* res, int32_t ldres, int32_t res_mode,
+                           void* y, void* stream);
+int stp3_linear_fwd_affine(int32_t M, int32_t K, int32_t N, const float* x, const float* w, int32_t ldw, const float* b,
+                           const float* coef, int32_t ldcoef, int32_t act, float* y, void* stream);
+int stp3_dwconv2d_fwd_affine(const stp3_dwconv_dims* dims, const void* x, const float* w, const float* coef, int32_t act,
+                             void* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -643,6 +643,30 @@ __global__ __launch_bounds__(kThreads) void sum_n_kernel(int n, size_t nvec, Sum
     }
 }
 
+// ---- eval constants of every BatchNorm of a model, one launch (stp3_bn_eval_coefs) ----------------
+// Table-driven like stp3_conv2d_prep_weights: the table carries an exclusive scan of 256-lane blocks per layer, a workgroup
+// binary-searches its layer.  scale / shift are computed by the expression of bn_apply_fwd_kernel's eval branch (same
+// operations, same order: the fused eval epilogues of stp3_conv.hip / stp3_dwconv.hip then give the bits of the apply pass).
+__global__ __launch_bounds__(kThreads) void bn_eval_coefs_kernel(const stp3_bn_coef_entry* __restrict__ table, int n) {
+    const int64_t b = blockIdx.x;
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].first_block <= b) lo = mid; else hi = mid - 1;
+    }
+    const stp3_bn_coef_entry e = table[lo];
+    const int c = (int)(b - e.first_block) * kThreads + threadIdx.x;
+    if (c >= e.lanes) return;
+    float scale = 0.f, shift = 0.f;
+    if (c < e.channels) {
+        const float is = 1.0f / sqrtf(e.running_var[c] + e.eps);
+        scale = (e.gamma ? e.gamma[c] : 1.f) * is;
+        shift = (e.beta ? e.beta[c] : 0.f) - e.running_mean[c] * scale;
+    }
+    e.out[c] = scale;
+    e.out[e.lanes + c] = shift;
+}
+
 // ---- host side --------------------------------------------------------------------------------
 inline int status() {
     hipError_t e = hipGetLastError();
@@ -924,6 +948,16 @@ int stp3_bn_bwd_train(const stp3_bn_dims* p, const void* dy, const void* x, cons
     if (rc) return rc;
     return stp3_bn_apply_bwd(p, dy, x, sbias, res, oscale, mean, invstd, gamma, beta, sums, (double)p->N * p->rows, dx,
                              dres, stream);
+}
+
+int stp3_bn_eval_coefs(const stp3_bn_coef_entry* table, int32_t n_entries, int64_t total_blocks, void* stream) {
+    if (n_entries < 0 || total_blocks < 0) return STP3_EINVAL;
+    if (n_entries == 0 || total_blocks == 0) return STP3_OK;
+    if (!table) return STP3_EINVAL;
+    if (total_blocks >= (1LL << 31)) return STP3_EUNSUP;
+    hipLaunchKernelGGL(bn_eval_coefs_kernel, dim3((unsigned)total_blocks), dim3(kThreads), 0, (hipStream_t)stream, table,
+                       n_entries);
+    return status();
 }
 
 }  // extern "C"

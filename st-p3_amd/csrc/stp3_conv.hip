@@ -90,7 +90,12 @@ __device__ __forceinline__ int lds_piece(int r, int j) { return (r * 8 + (j ^ ((
 // the BatchNorm backward recomputes the tiles it needs from the 6x smaller block input (BWD_REDUCE: the two sums of the
 // BatchNorm backward against the incoming gradient dz; BWD_APPLY: the gradient at the convolution output).  Every mode
 // rounds the accumulators to bf16 first: the values are those the stored tensor held.
-enum { kModePlain = 0, kModeStats = 1, kModeBnAct = 2, kModeBwdReduce = 3, kModeBwdApply = 4 };
+// AFFINE is the eval forward of a conv -> BatchNorm -> activation (+ skip) layer (stp3_conv2d_fwd_affine): BNACT with the
+// constants of the RUNNING statistics (stp3_bn_eval_coefs), a convolution bias if the layer has one, the skip added before
+// or after the activation, zeros in the padded channel lanes, and an output row stride of its own -- the bits of
+// stp3_conv2d_fwd followed by the eval stp3_bn_apply_fwd, in one pass.
+enum { kModePlain = 0, kModeStats = 1, kModeBnAct = 2, kModeBwdReduce = 3, kModeBwdApply = 4, kModeAffine = 5 };
+constexpr bool mode_bwd(int m) { return m == kModeBwdReduce || m == kModeBwdApply; }
 
 struct EpiArgs {
     const uint16_t* add;        // PLAIN mode, bf16 output: y = bf16(bf16(conv + bias) + add[m][co]) -- the gradient of a skip
@@ -102,6 +107,11 @@ struct EpiArgs {
     const float* gsums;         // [2][Cout]: sum g, sum g * xhat over all replicas (BWD_APPLY)
     float inv_count;
     int ldz, act;
+    const uint16_t* res;        // AFFINE: the skip, [M][ldres] bf16 (16-byte pieces), added before / after the activation
+    int ldres, res_mode;        // (STP3_RES_*)
+    int cvalid;                 // AFFINE: channels that exist; the lanes [cvalid, Cout) are written as zeros
+    const float* sbias;         // AFFINE, tiled kernel: per-sample bias [N][cvalid] added in front of the BatchNorm (the pooled
+    int hw;                     // branch of an ASPP projection), folded into the shift; hw = Ho * Wo output pixels per sample
 };
 
 template <int ACT>
@@ -358,7 +368,7 @@ __global__ __launch_bounds__(256) void conv2d_igemm_kernel(ConvDims d, int tiles
             }
         }
     }
-    if (MODE == kModeBnAct || MODE == kModeBwdApply) {
+    if (MODE == kModeBnAct || MODE == kModeBwdApply || MODE == kModeAffine) {
         // a thread's pieces all hold the same 8 channels (256 threads are a multiple of the BN / 8 pieces of a pixel):
         // the per-channel constants live in registers.  Cout, ldy (and ldz) are multiples of 8 here (checked by the host).
         const int c = (tid % (BN / 8)) * 8, co = co0 + c;
@@ -389,6 +399,35 @@ __global__ __launch_bounds__(256) void conv2d_igemm_kernel(ConvDims d, int tiles
                 if (MODE == kModeBnAct) {
 #pragma unroll
                     for (int r = 0; r < 8; ++r) out[r] = epi_act<ACT>(fmaf(e0[r], cs[r], ct[r]));
+                } else if (MODE == kModeAffine) {
+                    // the statement of bn_apply_fwd_kernel (stp3_bnact.hip), operation for operation
+                    float rv[8];
+                    if (ep.res) {
+                        const uint4 g = *reinterpret_cast<const uint4*>(ep.res + (size_t)m * ep.ldres + co);
+                        const uint32_t gds[4] = {g.x, g.y, g.z, g.w};
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            rv[2 * r] = __uint_as_float(gds[r] << 16);
+                            rv[2 * r + 1] = __uint_as_float(gds[r] & 0xffff0000u);
+                        }
+                    }
+                    float sh[8];
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) sh[r] = ct[r];
+                    if (ep.sbias) {                            // shift = fma(sbias, scale, shift), as the apply kernel folds it
+                        const float* sb = ep.sbias + (size_t)(m / ep.hw) * ep.cvalid + co;
+#pragma unroll
+                        for (int r = 0; r < 8; ++r)
+                            if (co + r < ep.cvalid) sh[r] = fmaf(sb[r], cs[r], ct[r]);
+                    }
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) {
+                        float t = fmaf(e0[r], cs[r], sh[r]);
+                        if (ep.res && ep.res_mode == STP3_RES_BEFORE_ACT) t += rv[r];
+                        t = epi_act<ACT>(t);
+                        if (ep.res && ep.res_mode == STP3_RES_AFTER_ACT) t += rv[r];
+                        out[r] = co + r < ep.cvalid ? t : 0.f;
+                    }
                 } else {
                     const uint4 g = *reinterpret_cast<const uint4*>(ep.dz + (size_t)m * ep.ldz + co);
                     const uint32_t gds[4] = {g.x, g.y, g.z, g.w};
@@ -477,6 +516,7 @@ __global__ __launch_bounds__(256) void conv2d_igemm_kernel(ConvDims d, int tiles
 // operations in the same order as the scalar statements of the tiled kernel: same bits.)
 struct Chan8 {
     stp3_f32x2 cs[4], ct[4], mu[4], is[4], a2[4], a3[4];
+    uint32_t keep[4];           // AFFINE: bit masks of the channels that exist, per bf16 pair (zero-padded lanes read as zero)
 };
 
 template <int MODE>
@@ -486,10 +526,13 @@ __device__ __forceinline__ void load_chan8(Chan8& k, const EpiArgs& ep, int Cout
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             k.cs[r][h] = k.ct[r][h] = k.mu[r][h] = k.is[r][h] = k.a2[r][h] = k.a3[r][h] = 0.f;
+            if (MODE == kModeAffine && h == 0)
+                k.keep[r] = (c + 2 * r < ep.cvalid ? 0x0000ffffu : 0u) | (c + 2 * r + 1 < ep.cvalid ? 0xffff0000u : 0u);
             if (MODE >= kModeBnAct && ok) {
                 const int cc = c + 2 * r + h;
                 k.cs[r][h] = ep.coef[cc];
                 k.ct[r][h] = ep.coef[Cout + cc];
+                if (MODE == kModeAffine) continue;             // (coef = [scale | shift] only)
                 k.mu[r][h] = ep.coef[2 * Cout + cc];
                 k.is[r][h] = ep.coef[3 * Cout + cc];
                 if (MODE == kModeBwdApply) {
@@ -502,13 +545,17 @@ __device__ __forceinline__ void load_chan8(Chan8& k, const EpiArgs& ep, int Cout
 }
 
 // wds: the 8 rounded outputs (bf16 pairs); gds: the 8 incoming gradients (BWD_* modes); s1 / s2: the running sums (PLAIN /
-// STATS: sum, sum of squares; BWD_REDUCE: sum g, sum g * xhat); ow: the 8 results as bf16 pairs (BNACT / BWD_APPLY)
+// STATS: sum, sum of squares; BWD_REDUCE: sum g, sum g * xhat); ow: the 8 results as bf16 pairs (BNACT / BWD_APPLY / AFFINE).
+// AFFINE: gds holds the 8 values of the SKIP (zeros without one: res_mode STP3_RES_NONE), added before / after the activation;
+// the output and the skip of a zero-padded channel lane (k.keep) read as zero and its constants are zero (stp3_bn_eval_coefs):
+// the lane is written as zero, as bn_apply_fwd_kernel does.
 template <int MODE>
 __device__ __forceinline__ void epi8(const uint32_t (&wds)[4], const uint32_t (&gds)[4], const Chan8& k, int act,
-                                     stp3_f32x2 (&s1)[4], stp3_f32x2 (&s2)[4], uint32_t (&ow)[4]) {
+                                     stp3_f32x2 (&s1)[4], stp3_f32x2 (&s2)[4], uint32_t (&ow)[4], int res_mode = STP3_RES_NONE) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const stp3_f32x2 e0 = {__uint_as_float(wds[r] << 16), __uint_as_float(wds[r] & 0xffff0000u)};
+        const uint32_t wd = MODE == kModeAffine ? wds[r] & k.keep[r] : wds[r];
+        const stp3_f32x2 e0 = {__uint_as_float(wd << 16), __uint_as_float(wd & 0xffff0000u)};
         if (MODE == kModePlain || MODE == kModeStats) {
             s1[r] = s1[r] + e0;
             s2[r] = pk_fma(e0, e0, s2[r]);
@@ -518,6 +565,15 @@ __device__ __forceinline__ void epi8(const uint32_t (&wds)[4], const uint32_t (&
                 stp3_f32x2 out = pre;
                 if (act == STP3_ACT_SWISH) out = pre * pk_sigmoid(pre);
                 else if (act == STP3_ACT_RELU) out = stp3_f32x2{fmaxf(pre.x, 0.f), fmaxf(pre.y, 0.f)};
+                ow[r] = pack_bf16(out.x, out.y);
+            } else if (MODE == kModeAffine) {
+                const uint32_t gd = gds[r] & k.keep[r];
+                const stp3_f32x2 rv = {__uint_as_float(gd << 16), __uint_as_float(gd & 0xffff0000u)};
+                stp3_f32x2 out = pre;
+                if (res_mode == STP3_RES_BEFORE_ACT) out = out + rv;
+                if (act == STP3_ACT_SWISH) out = out * pk_sigmoid(out);
+                else if (act == STP3_ACT_RELU) out = stp3_f32x2{fmaxf(out.x, 0.f), fmaxf(out.y, 0.f)};
+                if (res_mode == STP3_RES_AFTER_ACT) out = out + rv;
                 ow[r] = pack_bf16(out.x, out.y);
             } else {
                 const stp3_f32x2 dz = {__uint_as_float(gds[r] << 16), __uint_as_float(gds[r] & 0xffff0000u)};
@@ -660,12 +716,17 @@ __global__ __launch_bounds__(256, 2) void pointwise_rows_kernel(ConvDims d, int 
                 if (MODE != kModePlain || stat_partial) {
                     const uint32_t wds[4] = {v.x, v.y, v.z, v.w};
                     uint32_t gds[4] = {0u, 0u, 0u, 0u}, ow[4];
-                    if (MODE >= kModeBwdReduce) {
+                    if (mode_bwd(MODE)) {
                         const uint4 g = *reinterpret_cast<const uint4*>(ep.dz + (size_t)m * ep.ldz + cch);
                         gds[0] = g.x; gds[1] = g.y; gds[2] = g.z; gds[3] = g.w;
                     }
-                    epi8<MODE>(wds, gds, kc, ep.act, s1, s2, ow);
-                    if (MODE == kModeBnAct || MODE == kModeBwdApply)
+                    if (MODE == kModeAffine && ep.res) {
+                        const uint4 g = *reinterpret_cast<const uint4*>(ep.res + (size_t)m * ep.ldres + cch);
+                        gds[0] = g.x; gds[1] = g.y; gds[2] = g.z; gds[3] = g.w;
+                    }
+                    if (MODE == kModeAffine) epi8<MODE>(wds, gds, kc, ep.act, s1, s2, ow, ep.res ? ep.res_mode : STP3_RES_NONE);
+                    else epi8<MODE>(wds, gds, kc, ep.act, s1, s2, ow);
+                    if (MODE == kModeBnAct || MODE == kModeBwdApply || MODE == kModeAffine)
                         *reinterpret_cast<uint4*>(y + (size_t)m * d.ldy + cch) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
                     if (with_dx)                            // dy replaces the recomputed output in the wave's tile
                         *reinterpret_cast<uint4*>(tile + p * LDT + cl) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
@@ -797,10 +858,15 @@ __global__ __launch_bounds__(256) void pointwise_direct_kernel(ConvDims d, int k
         const int m = t * 32 + px;
         const bool row_ok = m < d.M;
         uint4 g[2] = {make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)};
-        if (MODE >= kModeBwdReduce) {
+        if (mode_bwd(MODE)) {
 #pragma unroll
             for (int s = 0; s < 2; ++s)
                 if (row_ok && ok[s]) g[s] = *reinterpret_cast<const uint4*>(ep.dz + (size_t)m * ep.ldz + ch[s]);
+        }
+        if (MODE == kModeAffine && ep.res) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+                if (row_ok && ok[s]) g[s] = *reinterpret_cast<const uint4*>(ep.res + (size_t)m * ep.ldres + ch[s]);
         }
         f32x16 acc;
 #pragma unroll
@@ -825,8 +891,9 @@ __global__ __launch_bounds__(256) void pointwise_direct_kernel(ConvDims d, int k
             }
             const uint32_t gds[4] = {g[s].x, g[s].y, g[s].z, g[s].w};
             uint32_t ow[4];
-            epi8<MODE>(wds, gds, kc[s], ep.act, s1[s], s2[s], ow);
-            if (MODE == kModeBnAct || MODE == kModeBwdApply)
+            if (MODE == kModeAffine) epi8<MODE>(wds, gds, kc[s], ep.act, s1[s], s2[s], ow, ep.res ? ep.res_mode : STP3_RES_NONE);
+            else epi8<MODE>(wds, gds, kc[s], ep.act, s1[s], s2[s], ow);
+            if (MODE == kModeBnAct || MODE == kModeBwdApply || MODE == kModeAffine)
                 *reinterpret_cast<uint4*>(y + (size_t)m * d.ldy + ch[s]) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
         }
 #pragma unroll
@@ -1328,6 +1395,7 @@ int pointwise_rows_launch_mode(int mode, const ConvDims& d, int ksteps, int tile
         case kModePlain: return pointwise_rows_launch_one<PP, KMAX, kModePlain>(d, ksteps, tiles_co, nwg, lds, x, w, y, partial, ep, s);
         case kModeStats: return pointwise_rows_launch_one<PP, KMAX, kModeStats>(d, ksteps, tiles_co, nwg, lds, x, w, y, partial, ep, s);
         case kModeBnAct: return pointwise_rows_launch_one<PP, KMAX, kModeBnAct>(d, ksteps, tiles_co, nwg, lds, x, w, y, partial, ep, s);
+        case kModeAffine: return pointwise_rows_launch_one<PP, KMAX, kModeAffine>(d, ksteps, tiles_co, nwg, lds, x, w, y, partial, ep, s);
         case kModeBwdReduce:
             return pointwise_rows_launch_one<PP, KMAX, kModeBwdReduce>(d, ksteps, tiles_co, nwg, lds, x, w, y, partial, ep, s);
         default: return pointwise_rows_launch_one<PP, KMAX, kModeBwdApply>(d, ksteps, tiles_co, nwg, lds, x, w, y, partial, ep, s);
@@ -1366,6 +1434,7 @@ int pointwise_direct_launch_mode(int mode, const ConvDims& d, int ksteps, unsign
         case kModePlain: return pointwise_direct_launch_one<KMAX, kModePlain>(d, ksteps, gx, parts, x, w, y, partial, ep, s);
         case kModeStats: return pointwise_direct_launch_one<KMAX, kModeStats>(d, ksteps, gx, parts, x, w, y, partial, ep, s);
         case kModeBnAct: return pointwise_direct_launch_one<KMAX, kModeBnAct>(d, ksteps, gx, parts, x, w, y, partial, ep, s);
+        case kModeAffine: return pointwise_direct_launch_one<KMAX, kModeAffine>(d, ksteps, gx, parts, x, w, y, partial, ep, s);
         case kModeBwdReduce: return pointwise_direct_launch_one<KMAX, kModeBwdReduce>(d, ksteps, gx, parts, x, w, y, partial, ep, s);
         default: return pointwise_direct_launch_one<KMAX, kModeBwdApply>(d, ksteps, gx, parts, x, w, y, partial, ep, s);
     }
@@ -1391,7 +1460,7 @@ int pointwise_run(const ConvDims& d, const void* x, const void* w, void* y, floa
     // in-cache 64 -> 128 @200x200x12: 46 / 36 / 31 us)
     const bool rows_small = (d.Cout == 144 || d.Cout == 192) && ksteps <= 2;
     const bool rows_lines = d.Cout % 64 == 0;
-    if ((rows_small || rows_lines) && d.ldy % 8 == 0 && (mode < kModeBwdReduce || ep.ldz % 8 == 0)) {
+    if ((rows_small || rows_lines) && d.ldy % 8 == 0 && (!mode_bwd(mode) || ep.ldz % 8 == 0)) {
         const int pp = rows_small ? d.Cout / 8 : (d.Cout % 128 == 0 ? 16 : 8), nt = (pp + 3) / 4;
         const int tiles_co = d.Cout / (pp * 8);
         if (ep.dx && !(rows_small && mode == kModeBwdApply && d.Cin <= 32)) return STP3_EUNSUP;
@@ -1434,10 +1503,12 @@ int igemm_run(const stp3_conv_dims* p, const void* x, const void* w, const float
     if (y && ((uintptr_t)y & (p->out_dtype == STP3_DTYPE_F32 ? 3 : 1))) return STP3_EUNSUP;
     if ((sums || mode != kModePlain) && p->out_dtype != STP3_DTYPE_BF16) return STP3_EUNSUP;
     if (mode != kModePlain) {
-        // the fused-BatchNorm modes: whole 16-byte channel pieces on every side, no convolution bias
-        if (p->has_bias || p->Cout % 8 || p->ldy % 8 || (y && ((uintptr_t)y & 15))) return STP3_EUNSUP;
+        // the fused-BatchNorm modes: whole 16-byte channel pieces on every side, no convolution bias (AFFINE takes one: the
+        // layer then runs on the tiled kernel, as it does in plain mode)
+        if ((p->has_bias && mode != kModeAffine) || p->Cout % 8 || p->ldy % 8 || (y && ((uintptr_t)y & 15))) return STP3_EUNSUP;
         if (mode >= kModeBnAct && !ep.coef) return STP3_EINVAL;
-        if (mode >= kModeBwdReduce && (!ep.dz || ep.ldz % 8 || ep.ldz < p->Cout || ((uintptr_t)ep.dz & 15))) return STP3_EUNSUP;
+        if (mode == kModeAffine && ep.res && (ep.ldres % 8 || ep.ldres < p->Cout || ((uintptr_t)ep.res & 15))) return STP3_EUNSUP;
+        if (mode_bwd(mode) && (!ep.dz || ep.ldz % 8 || ep.ldz < p->Cout || ((uintptr_t)ep.dz & 15))) return STP3_EUNSUP;
         if (mode == kModeBwdApply && !ep.gsums) return STP3_EINVAL;
         if ((mode == kModeStats || mode == kModeBwdReduce) && !sums) return STP3_EINVAL;
     }
@@ -1473,6 +1544,7 @@ int igemm_run(const stp3_conv_dims* p, const void* x, const void* w, const float
             ((uintptr_t)ep.add & 15) || ((uintptr_t)y & 15))
             return STP3_EUNSUP;
     } else if (pointwise_applies(p, y)) {
+        if (ep.sbias) return STP3_EUNSUP;                      // (the per-sample bias lives in the tiled kernel's epilogue only)
         ep.act = act;
         return pointwise_run(d, x, w, y, sums, partial, gx, s, mode, ep);
     }
@@ -1501,6 +1573,7 @@ int igemm_run(const stp3_conv_dims* p, const void* x, const void* w, const float
         case kModePlain: STP3_IGEMM_MODE(kModePlain); break;
         case kModeStats: STP3_IGEMM_MODE(kModeStats); break;
         case kModeBnAct: STP3_IGEMM_MODE(kModeBnAct); break;
+        case kModeAffine: STP3_IGEMM_MODE(kModeAffine); break;
         case kModeBwdReduce: STP3_IGEMM_MODE(kModeBwdReduce); break;
         default: STP3_IGEMM_MODE(kModeBwdApply); break;
     }
@@ -1539,6 +1612,22 @@ int stp3_conv2d_fwd_bnact(const stp3_conv_dims* p, const void* x, const void* w,
     EpiArgs ep = EpiArgs();
     ep.coef = coef;
     return igemm_run(p, x, w, nullptr, y, nullptr, nullptr, 0, stream, kModeBnAct, act, ep);
+}
+
+// ---- the eval forward of a conv -> BatchNorm -> activation (+ skip) layer in one pass (see kModeAffine) -----------------
+int stp3_conv2d_fwd_affine(const stp3_conv_dims* p, const void* x, const void* w, const float* bias, const float* coef,
+                           const float* sbias, int32_t channels, int32_t act, const void* res, int32_t ldres, int32_t res_mode,
+                           void* y, void* stream) {
+    if (!p || !coef) return STP3_EINVAL;
+    if (act != STP3_ACT_NONE && act != STP3_ACT_RELU && act != STP3_ACT_SWISH) return STP3_EINVAL;
+    if (res_mode != STP3_RES_NONE && res_mode != STP3_RES_BEFORE_ACT && res_mode != STP3_RES_AFTER_ACT) return STP3_EINVAL;
+    if ((res_mode != STP3_RES_NONE) != (res != nullptr)) return STP3_EINVAL;
+    if (channels <= 0 || channels > p->Cout) return STP3_EINVAL;
+    if (p->Cout != (channels + 7) / 8 * 8) return STP3_EUNSUP;          // the BatchNorm's channels, zero-padded to whole pieces
+    EpiArgs ep = EpiArgs();
+    ep.coef = coef; ep.res = (const uint16_t*)res; ep.ldres = ldres; ep.res_mode = res_mode; ep.cvalid = channels;
+    ep.sbias = sbias; ep.hw = p->Ho > 0 && p->Wo > 0 ? p->Ho * p->Wo : 1;
+    return igemm_run(p, x, w, bias, y, nullptr, nullptr, 0, stream, kModeAffine, act, ep);
 }
 
 int stp3_conv2d_bn_bwd_reduce(const stp3_conv_dims* p, const void* x, const void* w, const void* dz, int32_t ldz,

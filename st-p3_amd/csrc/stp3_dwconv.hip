@@ -85,10 +85,15 @@ __device__ __forceinline__ int xcd_order(int bid, int nwg) {
 // FLIP: the taps are read in reverse order -- the data gradient of a stride-1 depthwise convolution IS a depthwise
 // convolution of dy with the flipped kernel (padding K - 1 - p), so it shares this kernel and its register reuse
 // (TW outputs per thread share one input span per kernel row; the tap-major weights are read once per row).
-template <typename T, int K, int S, int TW, bool FLIP, typename Off>
+// AFFINE (stp3_dwconv2d_fwd_affine: the eval forward of an MBConv block): the eval BatchNorm and the activation are applied
+// where the output is written -- the accumulator is rounded to the tensor's type first (the value the stored route keeps in
+// memory), then act(fma(v, scale, shift)) in float32 as bn_apply_fwd_kernel's eval branch evaluates it, one rounding: the bits of
+// stp3_dwconv2d_fwd followed by the eval stp3_bn_apply_fwd, without the second pass.  coef = [scale | shift][C].
+template <typename T, int K, int S, int TW, bool FLIP, typename Off, bool AFFINE = false>
 __global__ __launch_bounds__(256) void dwconv_fwd_kernel(DwDims d, const T* __restrict__ x,
                                                          const float* __restrict__ w, const float* __restrict__ bias,
-                                                         T* __restrict__ y) {
+                                                         T* __restrict__ y, const float* __restrict__ coef = nullptr,
+                                                         int act = STP3_ACT_NONE) {
     constexpr int VN = Vec<T>::N;
     const int CV = d.C / VN;
     const int wgroups = (d.Wo + TW - 1) / TW;
@@ -141,11 +146,33 @@ __global__ __launch_bounds__(256) void dwconv_fwd_kernel(DwDims d, const T* __re
                 for (int j = 0; j < VN; ++j) acc[o][j] = fmaf(xin[o * S + kw][j], wk[kw][j], acc[o][j]);
     }
     const Off yrow = ((Off)(n * d.Ho + ho) * d.Wo) * pix + (Off)c0 * sizeof(T);
+    float cs[VN], ct[VN];
+    if (AFFINE) {
+#pragma unroll
+        for (int j = 0; j < VN; ++j) {
+            cs[j] = coef[c0 + j];
+            ct[j] = coef[d.C + c0 + j];
+        }
+    }
 #pragma unroll
     for (int o = 0; o < TW; ++o) {
         if (wo0 + o < d.Wo) {
             Vec<T> v;
             v.from_float(acc[o]);
+            if (AFFINE) {
+                float t[VN];
+                v.to_float(t);                                  // the rounded convolution output
+#pragma unroll
+                for (int j = 0; j < VN; ++j) t[j] = fmaf(t[j], cs[j], ct[j]);
+                if (act == STP3_ACT_SWISH) {
+#pragma unroll
+                    for (int j = 0; j < VN; ++j) t[j] = t[j] * fast_sigmoid(t[j]);
+                } else if (act == STP3_ACT_RELU) {
+#pragma unroll
+                    for (int j = 0; j < VN; ++j) t[j] = fmaxf(t[j], 0.f);
+                }
+                v.from_float(t);
+            }
             v.store(at(y, yrow + (Off)(wo0 + o) * pix));
         }
     }
@@ -610,10 +637,24 @@ int launch_fwd(const DwDims& d, const void* x, const float* w, const float* bias
     const int64_t total = (int64_t)d.N * d.Ho * ((d.Wo + TW - 1) / TW) * CV;
     if (small_tensors<T>(d))
         hipLaunchKernelGGL((dwconv_fwd_kernel<T, K, S, TW, false, uint32_t>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                           s, d, (const T*)x, w, bias, (T*)y);
+                           s, d, (const T*)x, w, bias, (T*)y, (const float*)nullptr, 0);
     else
         hipLaunchKernelGGL((dwconv_fwd_kernel<T, K, S, TW, false, uint64_t>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                           s, d, (const T*)x, w, bias, (T*)y);
+                           s, d, (const T*)x, w, bias, (T*)y, (const float*)nullptr, 0);
+    return status();
+}
+template <int K, int S>
+int launch_fwd_affine(const DwDims& d, const void* x, const float* w, const float* coef, int act, void* y, hipStream_t s) {
+    typedef uint16_t T;
+    constexpr int TW = 4;
+    const int CV = d.C / Vec<T>::N;
+    const int64_t total = (int64_t)d.N * d.Ho * ((d.Wo + TW - 1) / TW) * CV;
+    if (small_tensors<T>(d))
+        hipLaunchKernelGGL((dwconv_fwd_kernel<T, K, S, TW, false, uint32_t, true>), dim3((unsigned)((total + 255) / 256)), dim3(256),
+                           0, s, d, (const T*)x, w, (const float*)nullptr, (T*)y, coef, act);
+    else
+        hipLaunchKernelGGL((dwconv_fwd_kernel<T, K, S, TW, false, uint64_t, true>), dim3((unsigned)((total + 255) / 256)), dim3(256),
+                           0, s, d, (const T*)x, w, (const float*)nullptr, (T*)y, coef, act);
     return status();
 }
 template <typename T, int K, int S>
@@ -655,10 +696,10 @@ int launch_bwd_data(const DwDims& d, const void* dy, const float* w, void* dx, h
         const int64_t n = (int64_t)f.N * f.Ho * ((f.Wo + TW - 1) / TW) * (f.C / Vec<T>::N);
         if (small_tensors<T>(f))
             hipLaunchKernelGGL((dwconv_fwd_kernel<T, K, 1, TW, true, uint32_t>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                               f, (const T*)dy, w, (const float*)nullptr, (T*)dx);
+                               f, (const T*)dy, w, (const float*)nullptr, (T*)dx, (const float*)nullptr, 0);
         else
             hipLaunchKernelGGL((dwconv_fwd_kernel<T, K, 1, TW, true, uint64_t>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                               f, (const T*)dy, w, (const float*)nullptr, (T*)dx);
+                               f, (const T*)dy, w, (const float*)nullptr, (T*)dx, (const float*)nullptr, 0);
         return status();
     } else if constexpr (S == 2) {
         // quads: rows 2a - pt, 2a + 1 - pt for a = pt / 2 .. (H - 1 + pt) / 2
@@ -736,6 +777,19 @@ int stp3_dwconv2d_fwd_bias(const stp3_dwconv_dims* p, const void* x, const float
     if (rc) return rc;
     if (!x || !w || !y) return STP3_EINVAL;
     DISPATCH(launch_fwd, d, x, w, bias, y, (hipStream_t)stream);
+}
+
+int stp3_dwconv2d_fwd_affine(const stp3_dwconv_dims* p, const void* x, const float* w, const float* coef, int32_t act,
+                             void* y, void* stream) {
+    DwDims d; int vec;
+    int rc = check(p, &d, &vec);
+    if (rc) return rc;
+    if (!x || !w || !coef || !y) return STP3_EINVAL;
+    if (act != STP3_ACT_NONE && act != STP3_ACT_RELU && act != STP3_ACT_SWISH) return STP3_EINVAL;
+    if (p->dtype != STP3_DTYPE_BF16 || p->K == 7) return STP3_EUNSUP;       // the MBConv layers: bf16, 3x3 / 5x5
+    hipStream_t s = (hipStream_t)stream;
+    if (p->K == 3) return p->stride == 1 ? launch_fwd_affine<3, 1>(d, x, w, coef, act, y, s) : launch_fwd_affine<3, 2>(d, x, w, coef, act, y, s);
+    return p->stride == 1 ? launch_fwd_affine<5, 1>(d, x, w, coef, act, y, s) : launch_fwd_affine<5, 2>(d, x, w, coef, act, y, s);
 }
 
 int stp3_dwconv2d_fwd_stats_workspace(const stp3_dwconv_dims* p, size_t* bytes) {

@@ -20,7 +20,8 @@ constexpr int kLanes = 16;                  // lanes that share one output eleme
 // forward: element e = m * N + n
 __global__ __launch_bounds__(kT) void linear_fwd_kernel(int M, int K, int N, const float* __restrict__ x,
                                                         const float* __restrict__ w, int ldw, const float* __restrict__ b,
-                                                        float* __restrict__ y) {
+                                                        float* __restrict__ y, const float* __restrict__ coef, int ldcoef,
+                                                        int act) {
     const int lane = threadIdx.x & (kLanes - 1);
     const long e = ((long)blockIdx.x * kT + threadIdx.x) / kLanes;
     const bool ok = e < (long)M * N;
@@ -31,7 +32,17 @@ __global__ __launch_bounds__(kT) void linear_fwd_kernel(int M, int K, int N, con
     float acc = 0.f;
     for (int k = lane; k < K; k += kLanes) acc = fmaf(xr[k], wr[k], acc);
     acc = row16_sum(acc);
-    if (ok && lane == 0) y[e] = acc + (b ? b[n] : 0.f);
+    if (ok && lane == 0) {
+        float v = acc + (b ? b[n] : 0.f);
+        if (coef) {
+            // stp3_linear_fwd_affine: the eval BatchNorm + activation of the descriptor where it is written -- on the float32 value
+            // the stored route keeps, the statement of bn_apply_fwd_kernel's eval branch (stp3_bnact.hip): same bits, one launch
+            v = fmaf(v, coef[n], coef[ldcoef + n]);
+            if (act == STP3_ACT_RELU) v = fmaxf(v, 0.f);
+            else if (act == STP3_ACT_SWISH) v = v * fast_sigmoid(v);
+        }
+        y[e] = v;
+    }
 }
 
 // backward: elements [0, M*K) = dx, [M*K, M*K + N*K) = dw, then N of db; absent outputs (null) take no elements
@@ -81,7 +92,20 @@ int stp3_linear_fwd(int32_t M, int32_t K, int32_t N, const float* x, const float
     const int64_t elems = (int64_t)M * N;
     if (elems * kLanes >= (1LL << 31) * (int64_t)kT) return STP3_EUNSUP;
     const unsigned blocks = (unsigned)((elems * kLanes + kT - 1) / kT);
-    hipLaunchKernelGGL(linear_fwd_kernel, dim3(blocks), dim3(kT), 0, (hipStream_t)stream, (int)M, (int)K, (int)N, x, w, (int)ldw, b, y);
+    hipLaunchKernelGGL(linear_fwd_kernel, dim3(blocks), dim3(kT), 0, (hipStream_t)stream, (int)M, (int)K, (int)N, x, w, (int)ldw, b, y,
+                       (const float*)nullptr, 0, 0);
+    return status();
+}
+
+int stp3_linear_fwd_affine(int32_t M, int32_t K, int32_t N, const float* x, const float* w, int32_t ldw, const float* b,
+                           const float* coef, int32_t ldcoef, int32_t act, float* y, void* stream) {
+    if (M <= 0 || K <= 0 || N <= 0 || !x || !w || !y || !coef || ldw < K || ldcoef < N) return STP3_EINVAL;
+    if (act != STP3_ACT_NONE && act != STP3_ACT_RELU && act != STP3_ACT_SWISH) return STP3_EINVAL;
+    const int64_t elems = (int64_t)M * N;
+    if (elems * kLanes >= (1LL << 31) * (int64_t)kT) return STP3_EUNSUP;
+    const unsigned blocks = (unsigned)((elems * kLanes + kT - 1) / kT);
+    hipLaunchKernelGGL(linear_fwd_kernel, dim3(blocks), dim3(kT), 0, (hipStream_t)stream, (int)M, (int)K, (int)N, x, w, (int)ldw, b, y,
+                       coef, (int)ldcoef, (int)act);
     return status();
 }
 

@@ -91,6 +91,13 @@ class WprepEntry(ctypes.Structure):
                 ('ci_off', ctypes.c_int32), ('fwd_f32', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
+class BnCoefEntry(ctypes.Structure):
+    """struct stp3_bn_coef_entry (include/stp3_hip.h)."""
+    _fields_ = [('running_mean', ctypes.c_void_p), ('running_var', ctypes.c_void_p), ('gamma', ctypes.c_void_p),
+                ('beta', ctypes.c_void_p), ('out', ctypes.c_void_p), ('first_block', ctypes.c_int64),
+                ('channels', ctypes.c_int32), ('lanes', ctypes.c_int32), ('eps', ctypes.c_float), ('reserved', ctypes.c_int32)]
+
+
 class SeMlpDims(ctypes.Structure):
     """struct stp3_se_mlp_dims (include/stp3_hip.h)."""
     _fields_ = [('N', ctypes.c_int32), ('C', ctypes.c_int32), ('S', ctypes.c_int32), ('inv_rows', ctypes.c_float)]
@@ -273,6 +280,12 @@ SIGNATURES = {
                                      c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     'stp3_voxels_sum_fwd': (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     'stp3_voxels_sum_bwd': (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    'stp3_bn_eval_coefs': (c_int, [c_void_p, c_int32, ctypes.c_int64, c_void_p]),
+    'stp3_conv2d_fwd_affine': (c_int, [ctypes.POINTER(ConvDims), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                       c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    'stp3_linear_fwd_affine': (c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32,
+                                       c_void_p, c_void_p]),
+    'stp3_dwconv2d_fwd_affine': (c_int, [_DW_P, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
 }
 
 _lib = None

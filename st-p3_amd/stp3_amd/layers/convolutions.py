@@ -100,15 +100,14 @@ class ASPPConv(nn.Sequential):
                          nn.BatchNorm2d(out_channels), nn.ReLU())
         self.dilation = dilation
 
-    def conv_only(self, x):
-        """The convolution of the branch, with the taps that can never be in range dropped (exact)."""
+    def _kept_taps(self, x):
+        """(weight, padding, dilation) of the branch's convolution on ``x`` once the taps that can never be in range are
+        dropped (exact); only for maps no larger than the dilation in one direction at least."""
         conv = self[0]
         h, w = x.shape[-2:]
         d = self.dilation
         wgt = conv.weight
         rows, cols = (slice(1, 2) if d >= h else slice(None)), (slice(1, 2) if d >= w else slice(None))
-        if d < h and d < w:
-            return conv_module(conv, x)
         if wgt.shape[0] % 8 == 0 and x.shape[1] % 8 == 0 and ops.assembled_weight_supported(x, (wgt,)):
             # the taps that remain as a weight of their own, cut from the parameter by the launch that refreshes every bf16
             # shadow (ops.assembled_weight: no slice / cast / re-layout per step, and the gradient goes back the same way)
@@ -117,10 +116,18 @@ class ASPPConv(nn.Sequential):
         else:
             sub = wgt[:, :, rows, cols]
         if d >= h and d >= w:                       # only the centre tap can ever be in range
-            return conv2d(x, sub)
+            return sub, 0, 1
         if d >= h:                                  # centre row only: 1x3
-            return conv2d(x, sub, padding=(0, d), dilation=(1, d))
-        return conv2d(x, sub, padding=(d, 0), dilation=(d, 1))          # centre column only: 3x1
+            return sub, (0, d), (1, d)
+        return sub, (d, 0), (d, 1)                  # centre column only: 3x1
+
+    def conv_only(self, x):
+        """The convolution of the branch, with the taps that can never be in range dropped (exact)."""
+        h, w = x.shape[-2:]
+        if self.dilation < h and self.dilation < w:
+            return conv_module(self[0], x)
+        sub, padding, dilation = self._kept_taps(x)
+        return conv2d(x, sub, padding=padding, dilation=dilation)
 
     def forward(self, x):
         h, w = x.shape[-2:]
@@ -128,6 +135,12 @@ class ASPPConv(nn.Sequential):
             # no tap dropped: the plain conv -> BN -> ReLU chain, i.e. the operator whose convolution epilogue already
             # produces the BatchNorm statistics (one pass over the branch output less)
             return run_fused(self, x)
+        from . import fused
+        if fused.eval_coef(self[1]) is not None:
+            # the inference engine's scope: the eval BatchNorm + ReLU in the epilogue of the kept taps' convolution
+            sub, padding, dilation = self._kept_taps(x)
+            y = fused.eval_conv2d_bn_act(x, sub, None, 1, padding, dilation, self[1], ACT_RELU)
+            return y if y is not None else bn_act(self[1], conv2d(x, sub, padding=padding, dilation=dilation), ACT_RELU)
         return bn_act(self[1], self.conv_only(x), ACT_RELU)
 
 
@@ -147,6 +160,16 @@ class ASPPPooling(nn.Sequential):
     def forward(self, x):
         """Returns the (N, C, 1, 1) pooled descriptor; bilinear upsampling of a 1x1 map is a
         broadcast, which ``ASPP`` folds into its projection."""
+        from . import fused
+        coef = fused.eval_coef(self[2])
+        conv = self[1]
+        if coef is not None and x.is_cuda and torch.is_autocast_enabled() and conv.bias is None:
+            # the inference engine's scope: the descriptor's BatchNorm + ReLU in the launch of its 1x1 convolution -- the
+            # float32 product ``conv1x1_on_vector`` makes (autocast off), then the eval BatchNorm's statement on it: same bits
+            pooled, w2 = plane_mean(x).to(x.dtype).float(), conv.weight.float().flatten(1)     # (as ``conv_only`` rounds it)
+            if ops.small_linear_supported(pooled, w2):
+                y = ops.small_linear_affine(pooled, w2, None, coef, coef.numel() // 2, ACT_RELU)
+                return y.view(*y.shape, 1, 1)
         return bn_act(self[2], self.conv_only(x), ACT_RELU)   # the fused BatchNorm on N vectors
 
 
@@ -215,6 +238,12 @@ class ASPP(nn.Module):
             w_pool = ops.weight_columns(w_sp, proj.weight, n_sp, proj.weight.shape[1])
         else:
             w_sp, w_pool = proj.weight.split([n_sp, proj.weight.shape[1] - n_sp], dim=1)
+        from . import fused
+        if fused.eval_coef(bn) is not None:
+            # the inference engine's scope: the per-sample bias joins the BatchNorm in the projection's own epilogue
+            sbias = pooled_bias(hp(conv1x1_on_vector(pooled, w_pool).flatten(1)))
+            y = fused.eval_conv2d_bn_act(spatial, w_sp, None, 1, 0, 1, bn, ACT_RELU, sbias=sbias)
+            return drop(y if y is not None else bn_act(bn, conv2d(spatial, w_sp), ACT_RELU, sbias=sbias))
         y = conv2d(spatial, w_sp)
         # the pooled branch is a constant plane per sample: its projection is a per-sample bias, folded
         # into the fused BatchNorm instead of a broadcast add over the whole map

@@ -12,6 +12,7 @@ CPU tensors (the gloo data-parallel tests, the CPU port timed by ``bench.py``) t
 arithmetic written with torch ops.  GPU tensors never fall back: a
 missing ``libstp3hip.so`` raises.
 """
+import contextlib
 import os
 
 import torch
@@ -176,6 +177,13 @@ def bn_act(bn, x, act=ACT_NONE, res=None, res_mode=RES_NONE, sbias=None, oscale=
     counts in multiples of 8) read and write in place, with no pad / slice copies between the operators."""
     if res is None:
         res_mode = RES_NONE
+    if isinstance(x, PendingConv):
+        y = None
+        if sbias is None and oscale is None:
+            y = eval_conv2d_bn_act(*x.args, bn, act, res, res_mode, out_slot)
+        if y is not None:
+            return y
+        x = x.run()
     if (x.is_cuda and x.dim() == 5 and x.shape[3] == 1 and x.shape[4] == 1 and res is None and sbias is None
             and oscale is None):
         # BatchNorm3d of a (B, C, T, 1, 1) descriptor (the pyramid-pooling branch): per-channel statistics over the
@@ -221,6 +229,89 @@ def _kernel_args(bn, x, act, res, res_mode, sbias, oscale, out_slot=None):
             bn.num_features if x.shape[1] != bn.num_features else None, out_slot)
 
 
+# ---- the inference engine's scope (stp3_amd/inference.py) ---------------------------------------------------------------------
+# Inside it a conv -> BatchNorm (-> activation, + skip) layer whose BatchNorm runs on its running statistics takes ONE operator
+# (``ops.conv2d_affine`` / ``ops.depthwise_conv2d_affine``): the constants of every eval BatchNorm sit in the engine's arena
+# (``inference.EvalCoefficients``, written by one launch of stp3_bn_eval_coefs), the convolution's epilogue applies them.  Bit-equal
+# to the two operators of the plain path by construction (same convolution kernel, same rounding points), which stays what
+# ``model.eval()(...)`` runs OUTSIDE the scope: the engine's reference, and the only route for CPU / float64 / autograd.
+_EVAL_COEFS = None
+
+
+@contextlib.contextmanager
+def eval_fusion(coefs, gates=None):
+    """Scope of the inference engine's warm-up and capture.  ``coefs``: its ``EvalCoefficients``; ``gates``: its
+    ``ops_pred.EngineGateWeights`` (the merged GRU gate weights a captured graph reads must be buffers the engine rewrites in
+    place, not the entries of a cache that replaces them)."""
+    global _EVAL_COEFS
+    from .. import ops_pred
+    if torch.is_grad_enabled():
+        raise ops._lib.Stp3HipError('eval_fusion: the fused eval operators have no backward pass (enter it under torch.no_grad())')
+    prev, _EVAL_COEFS = _EVAL_COEFS, coefs
+    prev_stats, ops.EVAL_BACKWARD_STATS = ops.EVAL_BACKWARD_STATS, False     # (the layers left on ``bn_act`` keep no backward state)
+    prev_gates, ops_pred.ENGINE_GATES = ops_pred.ENGINE_GATES, gates
+    try:
+        yield coefs
+    finally:
+        _EVAL_COEFS, ops.EVAL_BACKWARD_STATS, ops_pred.ENGINE_GATES = prev, prev_stats, prev_gates
+
+
+def eval_coef(bn):
+    """The arena slice [scale | shift][lanes] of an eval BatchNorm inside the engine's scope; None outside it, for a layer in
+    training mode, and for a BatchNorm the arena does not hold."""
+    if _EVAL_COEFS is None or EMULATE_BF16 or bn.training or not bn.track_running_stats:
+        return None
+    return _EVAL_COEFS.lookup(bn)
+
+
+def eval_conv2d_bn_act(x, weight, cbias, stride, padding, dilation, bn, act, res=None, res_mode=RES_NONE, out_slot=None,
+                       sbias=None):
+    """The fused eval layer, or None when it does not qualify (the caller then takes its two operators, as outside the scope):
+    act(bn(conv2d(x, weight, cbias)) [+ res]) [+ res] with ``bn`` on its running statistics."""
+    if _EVAL_COEFS is None:
+        return None
+    coef = eval_coef(bn)
+    if coef is None or x.dim() != 4 or not _use_mfma(x, weight, stride):
+        return None
+    if res is None:
+        res_mode = RES_NONE
+    if not ops.conv2d_affine_supported(x, weight, stride, bn.num_features, res, out_slot, sbias, padding, cbias):
+        return None
+    return ops.conv2d_affine(x, weight, cbias, stride, padding, dilation, coef, bn.num_features, int(act), res, int(res_mode), out_slot,
+                             sbias)
+
+
+class PendingConv:
+    """A stride-1 convolution whose launch waits for the BatchNorm that consumes it: what a layer inside the engine's scope hands
+    to ``bn_act`` (directly or as the ``x`` of a ``bn_act_group`` member) in place of the convolution's result, so that the two
+    meet in ONE operator even where they are written far apart (the pointwise heads of ``temporal.TemporalBlock``).  Looks like
+    the result where the callers look at it (shape, dtype, ``is_cuda``, ``dim()``); ``bn_act`` launches it -- fused where the
+    layer qualifies, else the convolution and then the BatchNorm, as outside the scope."""
+
+    def __init__(self, x, weight, padding=0):
+        self.args = (x, weight, None, 1, padding, 1)
+        n, _, h, w = x.shape
+        kh, kw = weight.shape[2:]
+        ph, pw = ops._pair(padding)
+        self.shape = torch.Size((n, weight.shape[0], h + 2 * ph - kh + 1, w + 2 * pw - kw + 1))
+        self.dtype, self.is_cuda = torch.bfloat16, True
+
+    def dim(self):
+        return 4
+
+    def run(self):
+        return conv2d(*self.args)
+
+
+def _eval_fusable_conv_bn(conv, bn, x):
+    """A plain dense ``nn.Conv2d`` followed by an eval BatchNorm, inside the engine's scope (the eval twin of ``_fusable_conv_bn``)."""
+    return (_EVAL_COEFS is not None and isinstance(conv, nn.Conv2d) and isinstance(bn, nn.modules.batchnorm._BatchNorm)
+            and conv.groups == 1 and conv.padding_mode == 'zeros' and not isinstance(conv.padding, str) and x.dim() == 4
+            and not (conv.kernel_size == (1, 1) and x.shape[-2:] == (1, 1)) and eval_coef(bn) is not None
+            and _use_mfma(x, conv.weight, conv.stride)
+            and ops.conv2d_affine_supported(x, conv.weight, conv.stride, bn.num_features))
+
+
 def bn_act_group(items):
     """``bn_act`` for SIBLING layers -- parallel branches whose inputs do not depend on each other's outputs: with
     cross-replica statistics (N > 1 ranks) their exchanges travel together, one all-reduce forward and one backward for
@@ -257,6 +348,10 @@ def _run_member(it):
     if isinstance(it, dict):
         return bn_act(it['bn'], it['x'], it.get('act', ACT_NONE), it.get('res'), it.get('res_mode', RES_NONE), it.get('sbias'),
                       it.get('oscale'), it.get('out_slot'))
+    if it[0] == 'conv_bn_act_eval':                    # (the engine's scope: ``conv_bn_act_member``)
+        y = eval_conv2d_bn_act(*it[1])
+        # (None: the layer does not qualify after all -- its two operators, as outside the scope)
+        return y if y is not None else bn_act(it[1][6], conv2d(*it[1][:6]), it[1][7])
     from .. import ops_fused
     return ops_fused._ConvBnAct.apply(*it[1])
 
@@ -273,6 +368,8 @@ def conv_bn_act_member(x, conv, bn, act):
                                 ops.bn_momentum(bn), float(bn.eps), int(act),
                                 int(RES_NONE), ops._pair(conv.stride)[0], ops._pair(conv.padding), ops._pair(conv.dilation),
                                 group, None), bn)
+    if _eval_fusable_conv_bn(conv, bn, x):
+        return ('conv_bn_act_eval', (x, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation, bn, act), bn)
     return dict(bn=bn, x=conv_module(conv, x), act=act)
 
 
@@ -410,6 +507,10 @@ def conv_bn_act_layer(x, conv, bn, act, res=None, res_mode=RES_NONE):
         group = None if _sync_world(bn) > 1 else False
         return ops_fused.conv_bn_act(x, conv.weight, conv.bias, bn, act, res, res_mode if res is not None else RES_NONE,
                                      conv.stride, conv.padding, conv.dilation, group=group)
+    if _eval_fusable_conv_bn(conv, bn, x):
+        y = eval_conv2d_bn_act(x, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation, bn, act, res, res_mode)
+        if y is not None:
+            return y
     return bn_act(bn, conv_module(conv, x), act, res=res, res_mode=res_mode)
 
 
@@ -427,6 +528,13 @@ def run_fused(seq, x):
                                       m.stride, m.padding, m.dilation, group=group)
             i += 3 if relu else 2
             continue
+        if i + 1 < len(mods) and type(m) is nn.Conv2d and _eval_fusable_conv_bn(m, mods[i + 1], x):
+            relu = i + 2 < len(mods) and isinstance(mods[i + 2], nn.ReLU)
+            y = eval_conv2d_bn_act(x, m.weight, m.bias, m.stride, m.padding, m.dilation, mods[i + 1], ACT_RELU if relu else ACT_NONE)
+            if y is not None:                          # (None: the two operators below, as outside the scope)
+                x = y
+                i += 3 if relu else 2
+                continue
         if isinstance(m, nn.modules.batchnorm._BatchNorm):
             if i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU):
                 x = bn_act(m, x, ACT_RELU)

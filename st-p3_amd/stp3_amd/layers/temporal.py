@@ -118,6 +118,12 @@ class CausalConv3d(nn.Module):
             pieces = [ops.weight_piece(w, taps[k], 0, k * lanes_in) for k in range(kt)]
             if kt == 2:
                 x2 = ops.causal_pair(x2, frames)
+            from . import fused
+            if fused.eval_coef(self.norm) is not None:
+                # the inference engine's scope: the eval BatchNorm + ReLU in the convolution's epilogue (bit-equal, one pass)
+                wa = ops.assembled_weight((id(self), 'folded'), (_pad8(w.shape[0]), x2.shape[1], *w.shape[3:]), pieces)
+                y = fused.eval_conv2d_bn_act(x2, wa, None, 1, self._hw_pad[1:], 1, self.norm, ACT_RELU, out_slot=out_slot)
+                return y if y is not None else _bn_act_2d(self.norm, conv2d(x2, wa, None, 1, self._hw_pad[1:]), out_slot=out_slot)
             y = _conv2d_pieces(x2, (id(self), 'folded'), _pad8(w.shape[0]), w.shape[3:], pieces, padding=self._hw_pad[1:])
             return _bn_act_2d(self.norm, y, out_slot=out_slot)
         # (unbind / squeeze, not w[:, :, k]: the backward of k selects is k zero-fills, k copies and k - 1 additions; that of
@@ -291,8 +297,14 @@ class TemporalBlock(nn.Module):
             # parameter's other columns take their own way to the loss (below): its gradient is put together by autograd.
             piece = ops.weight_piece(conv.weight, conv.weight.detach().squeeze(2)[:, :c])
             token = []
-            y = _conv2d_pieces(x2, (id(conv), 'x'), wgt.shape[0] if lanes is None else lanes, (1, 1), [piece],
-                               direct=True if extra2 is None else 'shared', token_out=token)
+            out_ch = wgt.shape[0] if lanes is None else lanes
+            from . import fused
+            if extra2 is None and out_ch % 8 == 0 and fused.eval_coef(norm) is not None:
+                # the inference engine's scope: the convolution is launched by the BatchNorm that consumes it, as one operator
+                y = fused.PendingConv(x2, ops.assembled_weight((id(conv), 'x'), (out_ch, c, 1, 1), [piece]))
+            else:
+                y = _conv2d_pieces(x2, (id(conv), 'x'), out_ch, (1, 1), [piece],
+                                   direct=True if extra2 is None else 'shared', token_out=token)
             w_extra = None if extra2 is None else ops.weight_columns(token[0], conv.weight, c, wgt.shape[1])
         else:
             # (split, not two slices: one concatenation in backward instead of two zero-fills, two copies and an addition)

@@ -63,7 +63,16 @@ class StaticSamePadConv2d(nn.Conv2d):
             # squeeze-excite 1x1 convs on a pooled 1x1 map are plain GEMMs
             y = F.linear(x.flatten(1), self.weight.flatten(1), self.bias)
             return y.view(*y.shape, 1, 1)
-        if self.groups == 1 and x.is_cuda and self.in_channels % 8 and (torch.is_autocast_enabled() or x.dtype == torch.float32):
+        if self.groups == 1:
+            x, w = self._dense_operands(x)
+            return conv2d(x, w, self.bias, self.stride, 0, self.dilation)
+        if any(self._pad):
+            x = F.pad(x, self._pad)
+        return F.conv2d(x, self.weight, self.bias, self.stride, 0, self.dilation, self.groups)
+
+    def _dense_operands(self, x):
+        """(input with the frozen padding applied, weight) of the dense (groups == 1) layer: what ``conv2d`` is called with."""
+        if x.is_cuda and self.in_channels % 8 and (torch.is_autocast_enabled() or x.dtype == torch.float32):
             # the 3-channel stem: zero-pad the channels to 8 (together with the "same" padding, one copy) so that
             # it runs on the MFMA kernel too; the padded weight columns are zero and their gradient is dropped
             cp = (-self.in_channels) % 8
@@ -85,12 +94,28 @@ class StaticSamePadConv2d(nn.Conv2d):
                                           [ops.weight_piece(self.weight, self.weight.detach())])
             else:
                 wp = F.pad(self.weight, (0, 0, 0, 0, 0, cp))
-            return conv2d(x, wp, self.bias, self.stride, 0, self.dilation)
+            return x, wp
         if any(self._pad):
             x = F.pad(x, self._pad)
-        if self.groups == 1:
-            return conv2d(x, self.weight, self.bias, self.stride, 0, self.dilation)
-        return F.conv2d(x, self.weight, self.bias, self.stride, 0, self.dilation, self.groups)
+        return x, self.weight
+
+    def forward_bn_act(self, x, bn, act, res=None, res_mode=_fused.RES_NONE):
+        """act(bn(self(x))) (+ res).  Inside the inference engine's scope (``fused.eval_fusion``) a layer whose BatchNorm runs on
+        its running statistics is ONE operator -- the depthwise or the dense convolution with the BatchNorm in its epilogue,
+        bit-equal to the two operators it replaces; everywhere else, and for a layer that does not qualify, the two operators."""
+        coef = _fused.eval_coef(bn)
+        if coef is not None and x.is_cuda and x.dim() == 4:
+            if self.groups == self.in_channels == self.out_channels and self.groups > 1:
+                if (res is None and bn.num_features == self.out_channels
+                        and ops.depthwise_affine_supported(x, self.weight, self.stride)):
+                    return ops.depthwise_conv2d_affine(x, self.weight, self.stride[0], self._pad, coef, act)
+            elif self.groups == 1 and not (self.kernel_size == (1, 1) and x.shape[-2:] == (1, 1)) and x.dtype != torch.float64:
+                xp, w = self._dense_operands(x)
+                y = _fused.eval_conv2d_bn_act(xp, w, self.bias, self.stride, 0, self.dilation, bn, act, res, res_mode)
+                if y is not None:
+                    return y
+                return bn_act(bn, conv2d(xp, w, self.bias, self.stride, 0, self.dilation), act, res=res, res_mode=res_mode)
+        return bn_act(bn, self(x), act, res=res, res_mode=res_mode)
 
 
 # expand convolution -> BN0 -> swish through ops_fused._PointwiseBnAct (the convolution output is recomputed, never stored)
@@ -152,7 +177,7 @@ class MBConvBlock(nn.Module):
                 x = ops_fused.conv_bn_act(x, self._expand_conv.weight, None, self._bn0, ACT_SWISH, group=group,
                                           skip_carrier=carrier)
             else:
-                x = bn_act(self._bn0, self._expand_conv(x), ACT_SWISH)
+                x = self._expand_conv.forward_bn_act(x, self._bn0, ACT_SWISH)
         from .. import ops_fused
         if x.is_cuda and torch.is_autocast_enabled() and x.dtype == torch.float32:
             x = x.to(torch.get_autocast_dtype('cuda'))
@@ -162,7 +187,7 @@ class MBConvBlock(nn.Module):
             x = ops_fused.dw_bn_se(x, self._depthwise_conv, self._bn1, self._se_reduce, self._se_expand,
                                    group=None if _fused._sync_world(self._bn1) > 1 else False)
         elif x.is_cuda and x.dtype != torch.float64:
-            x = bn_act(self._bn1, self._depthwise_conv(x), ACT_SWISH)
+            x = self._depthwise_conv.forward_bn_act(x, self._bn1, ACT_SWISH)
             x = ops_fused.se_block(x, self._se_reduce, self._se_expand)
         else:
             x = bn_act(self._bn1, self._depthwise_conv(x), ACT_SWISH)
@@ -179,10 +204,9 @@ class MBConvBlock(nn.Module):
             return ops_fused.conv_bn_act(x, self._project_conv.weight, None, self._bn2, ACT_NONE, inputs if skip else None,
                                          RES_AFTER_ACT if skip else _fused.RES_NONE, group=group, oscale=oscale,
                                          res_carrier=carrier if skip else None)
-        x = self._project_conv(x)
-        if skip:
-            return bn_act(self._bn2, x, ACT_NONE, res=inputs, res_mode=RES_AFTER_ACT, oscale=oscale)
-        return bn_act(self._bn2, x, ACT_NONE)
+        if oscale is None:
+            return self._project_conv.forward_bn_act(x, self._bn2, ACT_NONE, res=inputs if skip else None, res_mode=RES_AFTER_ACT)
+        return bn_act(self._bn2, self._project_conv(x), ACT_NONE, res=inputs, res_mode=RES_AFTER_ACT, oscale=oscale)
 
 
 class EfficientNet(nn.Module):

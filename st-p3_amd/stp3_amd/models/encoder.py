@@ -9,7 +9,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..layers.convolutions import DeepLabHead, UpsamplingConcat
-from ..layers.fused import ACT_SWISH, bn_act
+from ..layers.fused import ACT_SWISH
 from .efficientnet import EfficientNet
 
 _REDUCTION_CHANNELS = {'b4': [0, 24, 32, 56, 160, 448], 'b0': [0, 16, 24, 40, 112, 320]}
@@ -85,7 +85,7 @@ class Encoder(nn.Module):
         plus the final tensor), encoder.py:59-82."""
         bb = self.backbone
         endpoints = []
-        x = bn_act(bb._bn0, bb._conv_stem(x), ACT_SWISH)
+        x = bb._conv_stem.forward_bn_act(x, bb._bn0, ACT_SWISH)
         n_blocks = len(bb._blocks)
         base_rate = bb._global_params.drop_connect_rate
         rates = [base_rate * float(idx) / n_blocks if base_rate else base_rate for idx in range(n_blocks)]

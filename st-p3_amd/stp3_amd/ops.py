@@ -801,6 +801,11 @@ def drive_exchange_group(gens, group):
     return results
 
 
+# False only inside ``layers.fused.eval_fusion`` (the inference engine's warm-up and capture, under torch.no_grad()): an eval
+# BatchNorm then keeps nothing for a backward pass.
+EVAL_BACKWARD_STATS = True
+
+
 class _BnAct(torch.autograd.Function):
     """y = act(BN(x + sbias) [+ res]) * oscale [+ res] on (N, C, H, W) tensors, channels-last memory."""
 
@@ -880,8 +885,11 @@ class _BnAct(torch.autograd.Function):
                                             y.data_ptr(), stream), 'stp3_bn_apply_fwd')
         else:
             count = 0.0
-            stat = torch.cat([running_mean.detach().float(), running_var.detach().float(), running_mean.detach().float(),
-                              torch.rsqrt(running_var.detach().float() + eps)])
+            # [mean | var | mean | invstd] for the backward pass; the inference engine's scope (no autograd: ``EVAL_BACKWARD_STATS``)
+            # does without these four small torch operators per layer
+            stat = None if not EVAL_BACKWARD_STATS else torch.cat(
+                [running_mean.detach().float(), running_var.detach().float(), running_mean.detach().float(),
+                 torch.rsqrt(running_var.detach().float() + eps)])
             check(lib.stp3_bn_apply_fwd(ctypes.byref(dims), x.data_ptr(), _opt_ptr(sb), _opt_ptr(res), _opt_ptr(osc),
                                         None, 0.0, _opt_ptr(gamma), _opt_ptr(beta), eps, 0.0, running_mean.data_ptr(),
                                         running_var.data_ptr(), None, None, y.data_ptr(), stream), 'stp3_bn_apply_fwd')
@@ -2205,3 +2213,119 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1, out_dtype=torc
     """Dense conv through the MFMA implicit-GEMM kernel (bf16 operands, float32 accumulation)."""
     s = _pair(stride)
     return _CONV_APPLY(x, weight, bias, s[0], _pair(padding), _pair(dilation), out_dtype)
+
+
+# ----------------------------------------------------------------------------------------------
+# Inference (stp3_amd/inference.py): convolution -> eval BatchNorm -> activation (+ skip) in one pass.  Forward only, no
+# autograd: the engine runs them under torch.no_grad().  Every operator here is bit-equal to the two operators it replaces
+# (``conv2d`` / ``depthwise_conv2d`` then the eval ``bn_act``): same convolution kernel and tiles, the same rounding points.
+# ----------------------------------------------------------------------------------------------
+def bn_eval_coefs(table, n_entries, total_blocks):
+    """One launch of stp3_bn_eval_coefs over a device table of stp3_bn_coef_entry (``inference.EvalCoefficients``)."""
+    check(_lib.lib().stp3_bn_eval_coefs(_ptr(table), int(n_entries), int(total_blocks), _stream()), 'stp3_bn_eval_coefs')
+
+
+POINTWISE_MAX_CIN = 128        # kPointwiseMaxCin of stp3_conv.hip (tests/test_inference_cpu.py holds the two together)
+
+
+def conv2d_affine_supported(x, weight, stride, channels, res=None, out_slot=None, sbias=None, padding=0, cbias=None):
+    """What stp3_conv2d_fwd_affine takes beyond ``conv2d_supported``: the BatchNorm's channels zero-padded to whole 16-byte
+    pieces of output lanes, a bf16 skip of the output's shape, an output slot on a 16-byte channel offset of a buffer whose
+    row is whole pieces; a per-sample bias (``sbias`` (N, channels) float32) only on the layers the TILED kernel runs -- not
+    the ones the library hands to its streaming pointwise kernels (1x1, stride 1, no padding, Cin <= 128, Cout >= 64, no
+    convolution bias: ``pointwise_applies`` in stp3_conv.hip, whose remaining conditions only narrow that set -- a layer this
+    keeps on two operators for nothing is slower, never refused by the library)."""
+    if not conv2d_supported(x, weight, stride):
+        return False
+    cout = weight.shape[0]
+    if sbias is not None:
+        if not (sbias.dim() == 2 and tuple(sbias.shape) == (x.shape[0], int(channels))):
+            return False
+        if (tuple(weight.shape[2:]) == (1, 1) and _pair(stride)[0] == 1 and _pair(padding) == (0, 0)
+                and weight.shape[1] <= POINTWISE_MAX_CIN
+                and cout >= 64 and cbias is None):
+            return False
+    if cout != (int(channels) + 7) // 8 * 8:
+        return False
+    if out_slot is not None and (out_slot[0].shape[1] % 8 or out_slot[1] % 8 or out_slot[0].dtype != torch.bfloat16):
+        return False
+    return res is None or (res.dim() == 4 and res.shape[1] == cout)
+
+
+def conv2d_affine(x, weight, bias, stride, padding, dilation, coef, channels, act, res=None, res_mode=RES_NONE, out_slot=None,
+                  sbias=None):
+    """act(scale * bf16(conv(x) + bias) + shift [+ res]) [+ res] -> bf16, through stp3_conv2d_fwd_affine.  ``coef``: float32
+    [scale | shift][Cout] of the layer's eval BatchNorm (a slice of the engine's arena); ``channels``: the BatchNorm's channel
+    count (Cout = channels rounded up to 8, zeros in the lanes beyond); ``out_slot`` = (buffer, first channel) as ``bn_act``."""
+    _need_gpu(x)
+    s, pad, dil = _pair(stride)[0], _pair(padding), _pair(dilation)
+    if x.dtype != torch.bfloat16:
+        x = x.to(torch.bfloat16)
+    wb, _ = _bf16_weights(weight)
+    fb = _f32(bias)
+    n, cin, h, w = x.shape
+    cout, _, kh, kw = wb.shape
+    x, ldx = _rows_view(x)
+    ho, wo = _conv_out(h, kh, s, pad[0], dil[0]), _conv_out(w, kw, s, pad[1], dil[1])
+    if out_slot is None:
+        y, ldy = torch.empty((n, cout, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last), cout
+    else:
+        buf, c0 = out_slot
+        if not (buf.is_contiguous(memory_format=torch.channels_last) and tuple(buf.shape[0:1] + buf.shape[2:]) == (n, ho, wo)
+                and buf.dtype == torch.bfloat16 and c0 % 8 == 0 and c0 + cout <= buf.shape[1]):
+            raise _lib.Stp3HipError('output slot does not fit the result (shape / dtype / channels-last / 16-byte channel offset)')
+        y, ldy = buf[:, c0:c0 + cout], buf.shape[1]
+    ldr = 0
+    if res is not None:
+        if tuple(res.shape) != (n, cout, ho, wo):
+            raise _lib.Stp3HipError('conv2d_affine: residual shape mismatch')
+        res, ldr = _rows_view(res if res.dtype == torch.bfloat16 else res.to(torch.bfloat16))
+    else:
+        res_mode = RES_NONE
+    dims = _lib.ConvDims(n, h, w, cin, ho, wo, cout, kh, kw, s, pad[0], pad[1], dil[0], dil[1], ldx, ldy, _lib.DTYPE_BF16,
+                         int(bias is not None))
+    sb = _f32(sbias)
+    check(_lib.lib().stp3_conv2d_fwd_affine(ctypes.byref(dims), _ptr(x), _ptr(wb), _opt_ptr(fb), _ptr(coef), _opt_ptr(sb), int(channels),
+                                            int(act), _opt_ptr(res), ldr, int(res_mode), _ptr(y), _stream()), 'stp3_conv2d_fwd_affine')
+    return y
+
+
+def small_linear_affine(x, w, b, coef, lanes, act):
+    """act(scale * (x W^T + b) + shift), float32, through stp3_linear_fwd_affine: ``small_linear`` with the eval BatchNorm of a
+    pooled descriptor in the same launch.  ``coef``: [scale | shift][lanes] of the arena."""
+    _need_gpu(x, w)
+    x = x.contiguous()
+    w, ldw = _rows_f32(w)
+    m, k = x.shape
+    n = w.shape[0]
+    y = torch.empty((m, n), dtype=torch.float32, device=x.device)
+    check(_lib.lib().stp3_linear_fwd_affine(m, k, n, x.data_ptr(), w.data_ptr(), ldw, _opt_ptr(b), coef.data_ptr(), int(lanes),
+                                            int(act), y.data_ptr(), _stream_handle()), 'stp3_linear_fwd_affine')
+    return y
+
+
+def depthwise_affine_supported(x, weight, stride):
+    """stp3_dwconv2d_fwd_affine: the bf16 3x3 / 5x5 layers of ``depthwise_supported``."""
+    if not depthwise_supported(x, weight, stride) or weight.shape[-1] not in (3, 5):
+        return False
+    return x.dtype == torch.bfloat16 or torch.is_autocast_enabled()
+
+
+def depthwise_conv2d_affine(x, weight, stride, pad, coef, act):
+    """act(scale * bf16(dwconv(x)) + shift) -> bf16 through stp3_dwconv2d_fwd_affine (arguments as ``depthwise_conv2d``)."""
+    _need_gpu(x, weight)
+    if x.dtype != torch.bfloat16:
+        x = x.to(torch.bfloat16)
+    c, _, k, _ = weight.shape
+    left, right, top, bottom = (int(p) for p in pad)
+    n, _, h, w = x.shape
+    stride = int(stride)
+    ho = (h + top + bottom - k) // stride + 1
+    wo = (w + left + right - k) // stride + 1
+    x = x.contiguous(memory_format=torch.channels_last)
+    wt = _dw_weight_taps(weight)
+    y = torch.empty((n, c, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    dims = _dw_dims(x, k, stride, top, left, ho, wo)
+    check(_lib.lib().stp3_dwconv2d_fwd_affine(ctypes.byref(dims), _ptr(x), _ptr(wt), _ptr(coef), int(act), _ptr(y), _stream()),
+          'stp3_dwconv2d_fwd_affine')
+    return y

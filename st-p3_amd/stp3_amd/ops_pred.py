@@ -115,10 +115,51 @@ def layer_norm_channels(x, weight, bias, eps, act=ACT_NONE):
 _GATE_WEIGHTS = {}        # (id(update weight), id(reset weight)) -> [stamp, merged bf16 weight, merged float32 bias]
 
 
+class EngineGateWeights:
+    """The merged gate weights and biases of ONE inference engine (``inference.InferenceEngine``): buffers the engine owns, at
+    addresses that never change, because its captured graph holds them.  ``_GATE_WEIGHTS`` below will not do there: it
+    replaces its tensors when the parameters change, and a graph captured on a cache hit would go on reading the old ones.
+    ``lookup`` allocates and fills a cell's pair on its first use (the engine's first warm-up forward) and only hands it out
+    afterwards; ``refresh`` rewrites every pair IN PLACE from the parameters' bf16 shadows and the biases as they are now."""
+
+    def __init__(self):
+        self.entries = {}           # (id(update conv), id(reset conv)) -> (update conv, reset conv, merged weight, merged bias)
+
+    @staticmethod
+    def _write(conv_update, conv_reset, wb, bias):
+        c = conv_update.out_channels
+        wb[:c].copy_(ops._bf16_weights(conv_update.weight)[0])
+        wb[c:].copy_(ops._bf16_weights(conv_reset.weight)[0])
+        bias[:c].copy_(conv_update.bias.detach())
+        bias[c:].copy_(conv_reset.bias.detach())
+
+    def lookup(self, conv_update, conv_reset):
+        key = (id(conv_update), id(conv_reset))
+        ent = self.entries.get(key)
+        if ent is None:
+            wu, wr = conv_update.weight, conv_reset.weight
+            wb = torch.empty((wu.shape[0] + wr.shape[0],) + tuple(wu.shape[1:]), dtype=torch.bfloat16, device=wu.device,
+                             memory_format=torch.channels_last)
+            bias = torch.empty(wu.shape[0] + wr.shape[0], dtype=torch.float32, device=wu.device)
+            self._write(conv_update, conv_reset, wb, bias)
+            ent = self.entries[key] = (conv_update, conv_reset, wb, bias)       # (the modules: their id() stays theirs)
+        return ent[2], ent[3]
+
+    def refresh(self):
+        for conv_update, conv_reset, wb, bias in self.entries.values():
+            self._write(conv_update, conv_reset, wb, bias)
+
+
+# Set inside ``layers.fused.eval_fusion`` only (the inference engine's warm-up and capture): the engine's ``EngineGateWeights``.
+ENGINE_GATES = None
+
+
 def _merged_gate_weights(conv_update, conv_reset):
     """The update and the reset gate read the same [x, state] operand: their two 3x3 convolutions run as ONE with the output
     channels concatenated (exact).  The merged bf16 weight is cut from the two parameters' bf16 shadows once per optimizer
     step (all time steps of a GRU share it), not once per cell."""
+    if ENGINE_GATES is not None:
+        return ENGINE_GATES.lookup(conv_update, conv_reset)
     wu, wr = conv_update.weight, conv_reset.weight
     key = (id(wu), id(wr))
     stamp = (ops.weight_stamp(wu), ops.weight_stamp(wr), wu.data_ptr(), wr.data_ptr(),
