@@ -788,6 +788,67 @@ int stp3_traj_cost_bwd(const stp3_plan_dims* dims, const float* grad_cost_fo, co
                        const float* cv_scale, float* grad_cost_volume, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Planner: the tail of an inference call (csrc/stp3_plan.hip) -- what the reference's callers run after the forward
+ * (evaluate.py:96-132, carla_agent.py:397-462) as two launches that a hipGraph can hold: nothing in them depends on the host.
+ *
+ * stp3_plan_scene -- the planner's view of the scene from the decoder's heads, one launch over the BEV grid: replaces
+ * evaluate.py:96-106,122 (argmax of the segmentation and pedestrian heads, logical_or) and the head of Rule / HeadwayCost /
+ * LR_divider.forward (stp3/cost.py:196-201, :258-263, :289-294: softmax of a logit pair, threshold).
+ *   segmentation [B][S][Cs][H][W], pedestrian [B][S][Cp][H][W] (Cp = 0: NULL), hdmap [B][4][H][W]: logits, float32 or bf16, any
+ *                element strides (channels-last included); float32 arithmetic after widening
+ *   occupancy [B][T][H][W] float32 = 1 where the argmax class of either head at frame first + t is != 0 (the first maximal
+ *                class wins a tie, a NaN counts as the maximum: torch.argmax), else 0
+ *   lane     [B][H][W] float32 = softmax probability of class 1 of channels 0:2, 0 where it is <= 0.5
+ *   drivable [B][H][W] float32 = softmax probability of class 1 of channels 2:4, 0 where it is <  0.5
+ * STP3_EINVAL: a null pointer, a size < 1, first < 0 or first + T > S; STP3_EUNSUP: another dtype, B or T + 1 > 65 535.
+ *
+ * stp3_plan_drive -- select and refine, one launch, one workgroup per sample: replaces the eval path of Planning.forward
+ * (stp3/models/planning_model.py:101-145: the command's third of the samples :103-115, Planning.select :47-64 with
+ * Cost_Function :26-47, the GRUCell / decoder loop :121-132).
+ *   dims, cost_volume (the sample stride given apart), occupancy, drivable, lane, target, footprint tables: as for
+ *   stp3_traj_cost_fwd, whose arithmetic scores the candidates (one shared device function); the batch's target sum is taken
+ *   inside.  trajs: N rows of T points per sample, float32, (lateral, forward[, heading ...]) with the strides of `drive`.
+ *   command [B] int32: 0 LEFT, 1 FORWARD, 2 RIGHT select the rows [k N / 3, (k + 1) N / 3), anything else all N rows; each
+ *   DISTINCT row is scored once.  total = cost_fc + (sum over t ascending of cost_fo[t]); the smallest total wins, the lowest
+ *   row index on an exact tie (a fixed-order reduction inside the workgroup).
+ *   cost_volume and h0 may be float32 or bf16 (drive->cv_dtype / h0_dtype; widened to float32 where they are read).
+ *   h0 [B][Hs]: the GRU state (the reduced front-camera features).  Per step x = [previous point (0 first), selected
+ *   point, target], torch.nn.GRUCell (gates r, z, n; n = tanh(W_in x + b_in + r (W_hn h + b_hn))), Linear - ReLU - Linear.
+ *   float32, every dot product one fused-multiply-add chain in ascending k (the last layer: 64 interleaved chains and a fixed
+ *   butterfly): bit-reproducible run to run.
+ *   final_traj [B][T][3] (third column 0), selected_traj [B][T][3] (the chosen row's first 3 columns; 0 where it has 2),
+ *   selected_index [B] int32 (a row of the N given).
+ * STP3_EINVAL: a null pointer, invalid dims, N % 3 != 0, Hs < 1, traj_cols < 2, a point stride below traj_cols, a negative
+ * stride.  STP3_EUNSUP: Hs not a multiple of 64 or > 512; more than 160 KB of LDS (4 (N (T + 1) + 8 Hs + 2056) bytes); 3 T > 1024;
+ * a stride of 2^31 elements or more; another dtype; a device ordinal >= 64.
+ * Both are answered before anything touches the GPU. */
+typedef struct stp3_scene_dims {
+    int32_t B, S, T, H, W;
+    int32_t Cs, Cp;                               /* classes of the two heads; Cp = 0: no pedestrian head */
+    int32_t first;                                /* first frame used: the model's receptive field */
+    int32_t seg_dtype, ped_dtype, hd_dtype;       /* STP3_DTYPE_* */
+    int64_t seg_stride[5], ped_stride[5];         /* elements: sample, frame, class, row, column */
+    int64_t hd_stride[4];                         /* elements: sample, channel, row, column */
+} stp3_scene_dims;
+int stp3_plan_scene(const stp3_scene_dims* dims, const void* segmentation, const void* pedestrian, const void* hdmap,
+                    float* occupancy, float* lane, float* drivable, void* stream);
+typedef struct stp3_drive_dims {
+    int32_t Hs;                                   /* GRU state size: a multiple of 64, <= 512 */
+    int32_t traj_cols;                            /* columns of a trajectory point (>= 2) */
+    int32_t cv_dtype, h0_dtype;                   /* STP3_DTYPE_* of cost_volume and h0 (bf16 is widened inside) */
+    int64_t traj_batch_stride, traj_row_stride, traj_point_stride;   /* floats */
+    int64_t cv_batch_stride;                      /* floats between the cost volumes of two samples ([T][H][W] is dense) */
+    const float* weights;                         /* one buffer of 4 Hs Hs + 27 Hs + 2 floats: GRUCell.weight_ih [3 Hs][6],
+                                                     bias_ih [3 Hs], weight_hh TRANSPOSED [Hs][3 Hs], bias_hh [3 Hs],
+                                                     decoder[0].weight TRANSPOSED [Hs][Hs], decoder[0].bias [Hs],
+                                                     decoder[2].weight [2][Hs], decoder[2].bias [2] */
+} stp3_drive_dims;
+int stp3_plan_drive(const stp3_plan_dims* dims, const stp3_drive_dims* drive, const float* trajs, const void* cost_volume,
+                    const float* occupancy, const float* drivable, const float* lane, const float* target,
+                    const int32_t* command, const int32_t* footprint0, const int32_t* footprint_lambda, const void* h0,
+                    float* final_traj, float* selected_traj, int32_t* selected_index, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Planner: the candidate set (csrc/stp3_sampler.hip) -- the reference's trajectory sampler, stp3/utils/sampler.py:8-146, as
  * its loaders call it (stp3/datas/NuscenesData.py:389-437: T0 = (0, 1), N0 = (1, 0) for kappa <= 0 else (-1, 0), frames
  * dt = 0.5 s apart, [:, ::10]): M trajectories per sample -- straight lines (:47-49), arcs about the curvature clamped to

@@ -127,6 +127,19 @@ class PlanDims(ctypes.Structure):
                                                'progress', 'volume', 'rule', 'w0', 'w1', 'headway_dist', 'lr_dist')])
 
 
+class SceneDims(ctypes.Structure):
+    """struct stp3_scene_dims (include/stp3_hip.h)."""
+    _fields_ = ([(k, ctypes.c_int32) for k in ('B', 'S', 'T', 'H', 'W', 'Cs', 'Cp', 'first', 'seg_dtype', 'ped_dtype', 'hd_dtype')] +
+                [('seg_stride', ctypes.c_int64 * 5), ('ped_stride', ctypes.c_int64 * 5), ('hd_stride', ctypes.c_int64 * 4)])
+
+
+class DriveDims(ctypes.Structure):
+    """struct stp3_drive_dims (include/stp3_hip.h)."""
+    _fields_ = ([(k, ctypes.c_int32) for k in ('Hs', 'traj_cols', 'cv_dtype', 'h0_dtype')] +
+                [(k, ctypes.c_int64) for k in ('traj_batch_stride', 'traj_row_stride', 'traj_point_stride', 'cv_batch_stride')] +
+                [('weights', ctypes.c_void_p)])
+
+
 class SamplerDims(ctypes.Structure):
     """struct stp3_sampler_dims (include/stp3_hip.h)."""
     _fields_ = ([(k, ctypes.c_int32) for k in ('B', 'M', 'n_left', 'n_straight', 'n_right', 'n_future')] +
@@ -268,6 +281,8 @@ SIGNATURES = {
     'stp3_warp_nearest': (c_int, [c_int32] * 4 + [c_void_p] * 5),
     'stp3_traj_cost_fwd': (c_int, [ctypes.POINTER(PlanDims)] + [c_void_p] * 14),
     'stp3_traj_cost_bwd': (c_int, [ctypes.POINTER(PlanDims)] + [c_void_p] * 5),
+    'stp3_plan_scene': (c_int, [ctypes.POINTER(SceneDims)] + [c_void_p] * 7),
+    'stp3_plan_drive': (c_int, [ctypes.POINTER(PlanDims), ctypes.POINTER(DriveDims)] + [c_void_p] * 14),
     'stp3_traj_sample': (c_int, [ctypes.POINTER(SamplerDims)] + [c_void_p] * 6),
     'stp3_instance_segment': (c_int, [c_int32] * 3 + [c_float] + [c_void_p] * 7),
     'stp3_instance_track': (c_int, [c_int32] * 4 + [c_float] + [c_void_p] * 5),

@@ -27,7 +27,8 @@ conv -> BatchNorm -> activation layer makes two full passes over its tensor.  ``
 
 Any configuration whose eval forward is free of host synchronisation can be captured: Perception.yml (N_FUTURE_FRAMES = 0) and
 the prediction stage (eval mode samples with zero noise, models/stp3.py ``distribution_forward``).  The planner call that
-follows the forward stays with the caller, as in evaluate.py:121-132: its ``commands`` are Python strings.
+follows the forward stays with the caller, as in evaluate.py:121-132 (or ``ops_plan.plan_scene`` + ``Planning.drive``): captured behind
+the forward it measured no faster per tick than issued eagerly while the replay runs (profiles/plan_engine_timing.txt).
 """
 import contextlib
 

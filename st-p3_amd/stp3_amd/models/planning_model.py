@@ -6,12 +6,14 @@
   2. training adds the max-margin loss against the expert trajectory (one more launch with N = 1);
   3. a GRU cell, started from the front camera's features (four stride-2 / channel-reducing ``Bottleneck``s: the
      library's MFMA convolutions), refines the selected trajectory point by point towards the target.
-The GRU cell and the two linear layers are torch operators on (B, 256) tensors: library GEMMs, a few microseconds each.
+In ``forward`` the GRU cell and the two linear layers are torch operators on (B, 256) tensors.  ``drive`` is the eval path without
+host dependence: selection and refinement in one launch of ``stp3_plan_drive``.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import ops_plan
 from ..cost import Cost_Function
 from ..layers.convolutions import Bottleneck
 
@@ -83,6 +85,28 @@ class Planning(nn.Module):
             else:
                 picked.append(traj)
         return torch.stack(picked)
+
+    def drive_weights(self, device):
+        """The weight copies ``stp3_plan_drive`` reads (``ops_plan.DriveWeights``), one set per device with static addresses;
+        rewritten in place when a parameter changed since they were cut (``load_state_dict``)."""
+        cache = self.__dict__.setdefault('_drive_weights', {})
+        key = str(device)
+        if key not in cache:
+            cache[key] = ops_plan.DriveWeights(self.GRU, self.decoder, device)
+        elif not cache[key].current():
+            cache[key].refresh()
+        return cache[key]
+
+    def drive(self, cam_front, trajs, cost_volume, occupancy, lane, drivable, command_codes, target_points, weights=None, out=None):
+        """The eval path of ``forward`` as two steps without host dependence: ``reduce_channel``, then ONE launch that scores the
+        command's candidates, selects the cheapest and refines it (``ops_plan.plan_drive``, stp3_plan_drive).
+        cam_front (B, C, fH, fW); trajs (B, N, T, >= 2) float32; cost_volume (B, T, H, W); occupancy (B, T, H, W), lane,
+        drivable (B, H, W): ``ops_plan.plan_scene``; command_codes (B,) int32: ``ops_plan.command_codes``; target_points (B, 2)
+        ->  (final_traj (B, T, 3), selected_traj (B, T, 3), selected_index (B,) int32).  ``weights``: the ``ops_plan.DriveWeights`` to
+        read instead of ``drive_weights``; ``out``: the three tensors to write."""
+        h = self.reduce_channel(cam_front).flatten(start_dim=1)          # (bf16 under autocast: the kernel widens it)
+        return ops_plan.plan_drive(self, trajs, cost_volume, occupancy, lane, drivable, command_codes, target_points, h,
+                                   weights=weights, out=out)
 
     def forward(self, cam_front, trajs, gt_trajs, cost_volume, semantic_pred, hd_map, commands, target_points):
         """cam_front (B, C, fH, fW); trajs (B, N, T, 3); gt_trajs (B, T, 3); cost_volume / semantic_pred (B, T, H, W);

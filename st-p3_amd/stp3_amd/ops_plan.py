@@ -234,3 +234,225 @@ def sample_trajectories(v0, kappa, n_future, sample_num, draws=None, generator=N
     _check(_lib.lib().stp3_traj_sample(ctypes.byref(d), ops._ptr(v0), ops._ptr(kappa), ops._ptr(draws), ops._ptr(trajs),
                                        ops._ptr(order) if return_order else None, ops._stream()), 'stp3_traj_sample')
     return (trajs, order) if return_order else trajs
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The planner tail of an inference call: stp3_plan_scene / stp3_plan_drive (csrc/stp3_plan.hip) for GPU tensors -- two launches
+# with no host dependence -- and the torch statements of the same steps, in the same operation order, for CPU tensors.
+# (Captured behind the forward in ``inference.InferenceEngine``'s graph they were no faster per tick than the eager statements
+# they replace, DESIGN.md section 4.12: the engine does not hold them.)
+
+COMMAND_CODES = {'LEFT': 0, 'FORWARD': 1, 'RIGHT': 2}
+COMMAND_ALL = 3                             # any other command: all N candidates (planning_model.py:114-115)
+DRIVE_MAX_STATE = 512
+_DTYPES = {torch.float32: 0, torch.bfloat16: 1}
+
+
+def command_codes(commands, device=None):
+    """(B,) int32: 0 LEFT, 1 FORWARD, 2 RIGHT, 3 for any other string -- the kernel's table of planning_model.py:103-115."""
+    if isinstance(commands, str) or not all(isinstance(c, str) for c in commands):
+        raise ValueError(f'commands must be a list of strings: {commands!r}')
+    return torch.tensor([COMMAND_CODES.get(c, COMMAND_ALL) for c in commands], dtype=torch.int32, device=device)
+
+
+def _scene_check(segmentation, pedestrian, hdmap, n_present):
+    if segmentation.ndim != 5 or hdmap.ndim != 4 or hdmap.shape[1] != 4:
+        raise ValueError(f'segmentation must be (B, S, C, H, W) and hdmap (B, 4, H, W): {tuple(segmentation.shape)}, {tuple(hdmap.shape)}')
+    B, S, _, H, W = segmentation.shape
+    if tuple(hdmap.shape) != (B, 4, H, W):
+        raise ValueError(f'hdmap {tuple(hdmap.shape)} does not fit segmentation {tuple(segmentation.shape)}')
+    if pedestrian is not None and (pedestrian.ndim != 5 or tuple(pedestrian.shape[:2]) != (B, S) or
+                                   tuple(pedestrian.shape[3:]) != (H, W) or pedestrian.device != segmentation.device):
+        raise ValueError(f'pedestrian {tuple(pedestrian.shape)} does not fit segmentation {tuple(segmentation.shape)}')
+    if not 0 <= int(n_present) < S:
+        raise ValueError(f'n_present = {n_present} with {S} frames')
+    if hdmap.device != segmentation.device:
+        raise ValueError('segmentation and hdmap are on different devices')
+
+
+def plan_scene_reference(segmentation, pedestrian, hdmap, n_present):
+    """``plan_scene`` as torch statements: evaluate.py:96-106,122 and the mask heads of cost.py (``lane_mask`` / ``drivable_mask``)."""
+    from .cost import drivable_mask, lane_mask
+    seg = torch.argmax(segmentation, dim=2)
+    ped = torch.argmax(pedestrian, dim=2) if pedestrian is not None else torch.zeros_like(seg)
+    occupancy = torch.logical_or(seg, ped)[:, int(n_present):]
+    return occupancy.float().contiguous(), lane_mask(hdmap[:, 0:2]).float(), drivable_mask(hdmap[:, 2:4]).float()
+
+
+def plan_scene(segmentation, pedestrian, hdmap, n_present, out=None):
+    """The planner's inputs from the decoder's heads: (occupancy (B, T, H, W), lane (B, H, W), drivable (B, H, W)) float32, T = S -
+    n_present.  ``segmentation`` (B, S, Cs, H, W), ``pedestrian`` (B, S, Cp, H, W) or None, ``hdmap`` (B, 4, H, W): float32 or bf16
+    logits in any layout.  GPU tensors: one launch of ``stp3_plan_scene``, into ``out`` (the three tensors) when given; CPU
+    tensors: ``plan_scene_reference``."""
+    _scene_check(segmentation, pedestrian, hdmap, n_present)
+    heads = [t for t in (segmentation, pedestrian, hdmap) if t is not None]
+    for t in heads:
+        if t.dtype not in _DTYPES:
+            raise ValueError(f'logits must be float32 or bfloat16: {t.dtype}')
+    if not segmentation.is_cuda:
+        return plan_scene_reference(segmentation, pedestrian, hdmap, n_present)
+    B, S, Cs, H, W = segmentation.shape
+    T = S - int(n_present)
+    d = _lib.SceneDims()
+    d.B, d.S, d.T, d.H, d.W, d.Cs, d.first = B, S, T, H, W, Cs, int(n_present)
+    d.Cp = 0 if pedestrian is None else pedestrian.shape[2]
+    d.seg_dtype, d.hd_dtype = _DTYPES[segmentation.dtype], _DTYPES[hdmap.dtype]
+    d.ped_dtype = 0 if pedestrian is None else _DTYPES[pedestrian.dtype]
+    d.seg_stride[:] = segmentation.stride()
+    d.hd_stride[:] = hdmap.stride()
+    if pedestrian is not None:
+        d.ped_stride[:] = pedestrian.stride()
+    dev = segmentation.device
+    if out is None:
+        out = (torch.empty(B, T, H, W, device=dev), torch.empty(B, H, W, device=dev), torch.empty(B, H, W, device=dev))
+    occupancy, lane, drivable = out
+    for t, shape in ((occupancy, (B, T, H, W)), (lane, (B, H, W)), (drivable, (B, H, W))):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f'out: expected a contiguous float32 {shape} tensor on {dev}, got {tuple(t.shape)} {t.dtype}')
+    _check(_lib.lib().stp3_plan_scene(ctypes.byref(d), ops._ptr(segmentation), ops._ptr(pedestrian) if pedestrian is not None else None,
+                                      ops._ptr(hdmap), ops._ptr(occupancy), ops._ptr(lane), ops._ptr(drivable), ops._stream()),
+           'stp3_plan_scene')
+    return occupancy, lane, drivable
+
+
+class DriveWeights:
+    """The copy of the planner's GRU cell and decoder that ``stp3_plan_drive`` reads: ONE float32 buffer (the layout of
+    ``stp3_drive_dims.weights``) with ``weight_hh`` and the first decoder layer TRANSPOSED -- consecutive threads read consecutive
+    addresses.  The buffer keeps its address (a captured graph could read it); ``refresh()`` rewrites it in place, ``current()`` tells
+    whether the parameters still have the versions the copy was cut from."""
+    NAMES = ('w_ih', 'b_ih', 'w_hh_t', 'b_hh', 'w1_t', 'b1', 'w2', 'b2')
+
+    def __init__(self, gru, decoder, device):
+        self.gru, self.decoder, self.device = gru, decoder, torch.device(device)
+        if gru.input_size != 6 or not gru.bias or decoder[0].in_features != gru.hidden_size or decoder[2].out_features != 2:
+            raise ValueError('plan_drive: the refinement is a GRUCell(6, Hs) with biases and Linear(Hs, Hs) - ReLU - Linear(Hs, 2)')
+        self.Hs = gru.hidden_size
+        sources = self._sources()
+        self.buffer = torch.empty(sum(v.numel() for v in sources.values()), dtype=torch.float32, device=self.device)
+        assert self.buffer.numel() == 4 * self.Hs * self.Hs + 27 * self.Hs + 2
+        self.buffers, at = {}, 0                               # views of the buffer, by name
+        for k, v in sources.items():
+            self.buffers[k] = self.buffer[at:at + v.numel()].view(v.shape)
+            at += v.numel()
+        self.versions = None
+        self.refresh()
+
+    def _params(self):
+        g, d = self.gru, self.decoder
+        return (g.weight_ih, g.bias_ih, g.weight_hh, g.bias_hh, d[0].weight, d[0].bias, d[2].weight, d[2].bias)
+
+    def _sources(self):
+        w_ih, b_ih, w_hh, b_hh, w1, b1, w2, b2 = (p.detach() for p in self._params())
+        return dict(zip(self.NAMES, (w_ih, b_ih, w_hh.t(), b_hh, w1.t(), b1, w2, b2)))
+
+    def current(self):
+        return self.versions == tuple((p.data_ptr(), p._version) for p in self._params())
+
+    def refresh(self):
+        with torch.no_grad():
+            for k, v in self._sources().items():
+                self.buffers[k].copy_(v)
+        self.versions = tuple((p.data_ptr(), p._version) for p in self._params())
+
+
+def _drive_check(trajs, cost_volume, occupancy, lane, drivable, codes, target, h0):
+    if trajs.ndim != 4 or trajs.shape[-1] < 2 or trajs.dtype != torch.float32:
+        raise ValueError(f'trajs must be float32 (B, N, T, >= 2): {tuple(trajs.shape)} {trajs.dtype}')
+    B, N, T, _ = trajs.shape
+    if N % 3 != 0 or N < 3:
+        raise ValueError(f'N = {N} candidates: one third per command, N % 3 must be 0')
+    if cost_volume.ndim != 4 or tuple(cost_volume.shape[:2]) != (B, T):
+        raise ValueError(f'cost_volume must be (B, T, H, W) = ({B}, {T}, H, W): {tuple(cost_volume.shape)}')
+    H, W = cost_volume.shape[-2:]
+    for name, t, shape in (('occupancy', occupancy, (B, T, H, W)), ('lane', lane, (B, H, W)), ('drivable', drivable, (B, H, W)),
+                           ('target', target, (B, 2)), ('command_codes', codes, (B,))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f'{name} must be {shape}: {tuple(t.shape)}')
+    if codes.dtype != torch.int32:
+        raise ValueError(f'command_codes must be int32 (ops_plan.command_codes): {codes.dtype}')
+    if h0.ndim != 2 or h0.shape[0] != B:
+        raise ValueError(f'h0 must be (B, Hs): {tuple(h0.shape)}')
+    if cost_volume.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(f'cost_volume dtype {cost_volume.dtype}')
+    return B, N, T, H, W
+
+
+def plan_drive_reference(planner, trajs, cost_volume, occupancy, lane, drivable, codes, target, h0):
+    """``plan_drive`` as torch statements in the kernel's operation order: every row scored by ``planner.cost_function``'s terms
+    (stp3_amd/cost.py; the masks enter as one-channel maps), total = cost_fc + sum_t cost_fo, the smallest total of the
+    command's range with the lowest index on an exact tie, then the GRUCell / decoder loop of ``Planning.forward``."""
+    B, N, T, _ = trajs.shape
+    fc, fo = planner.cost_function(cost_volume, trajs[..., :2], occupancy, lane[:, None], drivable[:, None], target)
+    total = fc + fo.sum(dim=-1)
+    rows = torch.arange(N, device=trajs.device)[None]
+    k = codes.long()[:, None]
+    third = N // 3
+    allowed = torch.where((k >= 0) & (k <= 2), (rows >= k * third) & (rows < (k + 1) * third), torch.ones_like(rows, dtype=torch.bool))
+    total = torch.where(allowed, total, torch.full_like(total, float('inf')))
+    lowest = total.min(dim=1, keepdim=True).values
+    # the first row that attains the minimum (all rows, should no total compare: the range's first row)
+    index = torch.where(total == lowest, rows, torch.full_like(rows, N)).min(dim=1).values
+    first = torch.where((k[:, 0] >= 0) & (k[:, 0] <= 2), k[:, 0] * third, torch.zeros_like(k[:, 0]))
+    index = torch.where(index == N, first, index)
+    chosen = trajs[torch.arange(B, device=trajs.device), index]
+    h = h0.to(planner.GRU.weight_hh.dtype)
+    tgt = target.to(h.dtype)
+    point = torch.zeros(B, 2, device=h.device, dtype=h.dtype)
+    refined = []
+    for i in range(T):
+        h = planner.GRU(torch.cat([point, chosen[:, i, :2].to(h.dtype), tgt], dim=-1), h)
+        point = planner.decoder(h)
+        refined.append(point)
+    refined = torch.stack(refined, dim=1)
+    final = torch.cat([refined, torch.zeros_like(refined[..., :1])], dim=-1)
+    selected = torch.zeros(B, T, 3, device=trajs.device, dtype=trajs.dtype)
+    cols = min(3, trajs.shape[-1])
+    selected[..., :cols] = chosen[..., :cols]
+    return final, selected, index.to(torch.int32)
+
+
+def plan_drive(planner, trajs, cost_volume, occupancy, lane, drivable, codes, target, h0, weights=None, out=None):
+    """Select and refine: (final_traj (B, T, 3), selected_traj (B, T, 3), selected_index (B,) int32).
+
+    ``planner``: the ``Planning`` module (its ``cost_function`` gives the grid constants and footprint tables, ``GRU`` / ``decoder``
+    the refinement).  ``trajs`` (B, N, T, >= 2) float32, any strides with a dense last axis; ``cost_volume`` (B, T, H, W);
+    ``occupancy`` / ``lane`` / ``drivable``: what ``plan_scene`` returns; ``codes`` (B,) int32 (``command_codes``); ``target``
+    (B, 2); ``h0`` (B, Hs).  GPU tensors: one launch of ``stp3_plan_drive`` reading ``weights`` (a ``DriveWeights``; default: the
+    planner's own, ``Planning.drive_weights``), results into ``out`` when given; CPU tensors: ``plan_drive_reference``."""
+    B, N, T, H, W = _drive_check(trajs, cost_volume, occupancy, lane, drivable, codes, target, h0)
+    if not trajs.is_cuda:
+        return plan_drive_reference(planner, trajs, cost_volume, occupancy, lane, drivable, codes, target, h0)
+    Hs = planner.GRU.hidden_size
+    if h0.shape[1] != Hs:
+        raise ValueError(f'h0 must be (B, {Hs}): {tuple(h0.shape)}')
+    if Hs % 64 != 0 or Hs > DRIVE_MAX_STATE:
+        raise _lib.Stp3HipError(f'stp3_plan_drive: GRU state size {Hs} (multiples of 64 up to {DRIVE_MAX_STATE})')
+    dev = trajs.device
+    weights = weights if weights is not None else planner.drive_weights(dev)
+    assert tuple(cost_volume.shape[-2:]) == tuple(int(v) for v in planner.cost_function.safetycost.bev_dimension[:2])
+    fp0, fpl, params = planner.cost_function._kernel_inputs(dev)
+    if trajs.stride(-1) != 1:
+        trajs = trajs.contiguous()
+    # bf16 tensors (the heads under autocast) are widened inside the kernel: no conversion launch
+    if cost_volume.dtype not in _DTYPES or not cost_volume[0].is_contiguous():
+        cost_volume = cost_volume.float().contiguous()
+    if h0.dtype not in _DTYPES or not h0.is_contiguous():
+        h0 = h0.float().contiguous()
+    occupancy, lane, drivable = (t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous()
+                                 for t in (occupancy, lane, drivable))
+    target = target.float().contiguous()
+    d = _dims(params, B, N, T, H, W, fp0.shape[0], fpl.shape[0])
+    q = _lib.DriveDims()
+    q.Hs, q.traj_cols, q.cv_dtype, q.h0_dtype = Hs, trajs.shape[-1], _DTYPES[cost_volume.dtype], _DTYPES[h0.dtype]
+    q.traj_batch_stride, q.traj_row_stride, q.traj_point_stride = trajs.stride()[:3]
+    q.cv_batch_stride = cost_volume.stride(0)
+    q.weights = weights.buffer.data_ptr()
+    if out is None:
+        out = (torch.empty(B, T, 3, device=dev), torch.empty(B, T, 3, device=dev), torch.empty(B, device=dev, dtype=torch.int32))
+    final, selected, index = out
+    _check(_lib.lib().stp3_plan_drive(ctypes.byref(d), ctypes.byref(q), ops._ptr(trajs), ops._ptr(cost_volume), ops._ptr(occupancy),
+                                      ops._ptr(drivable), ops._ptr(lane), ops._ptr(target), ops._ptr(codes), ops._ptr(fp0), ops._ptr(fpl),
+                                      ops._ptr(h0), ops._ptr(final), ops._ptr(selected), ops._ptr(index), ops._stream()),
+           f'stp3_plan_drive (B {B}, N {N}, T {T}, grid {H} x {W}, footprints {fp0.shape[0]} / {fpl.shape[0]}, Hs {Hs}, trajs strides '
+           f'{tuple(trajs.stride())}, cost volume stride {cost_volume.stride(0)}, cells {params["dx0"]} x {params["dx1"]} m)')
+    return final, selected, index
