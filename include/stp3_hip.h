@@ -1050,6 +1050,76 @@ int stp3_linear_fwd_affine(int32_t M, int32_t K, int32_t N, const float* x, cons
 int stp3_dwconv2d_fwd_affine(const stp3_dwconv_dims* dims, const void* x, const float* w, const float* coef, int32_t act,
                              void* y, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Depth labels from LiDAR points (csrc/stp3_depth.hip): batch['depths'] of LIFT.GT_DEPTH.
+ *
+ * What is restated (the header of csrc/stp3_depth.hip gives the arithmetic):
+ *   (a) projection: NuScenesExplorer.map_pointcloud_to_image of the nuScenes devkit -- third-party, restated from its
+ *       published source, PARITY UNPINNED;
+ *   (b) scatter, last point wins: stp3/datas/NuscenesData.py:291-293;
+ *   (c) bilinear resample (align_corners=False) of the whole map, crop, round half to even: :294-299 and :261-266;
+ *   (d) class ids: stp3/trainer.py:269-276.
+ * Inputs of a batch of F frames x N cameras:
+ *   points      [n_total][3] float32, the sweeps of all frames one after the other
+ *   offsets     [F + 1] int32 ON THE DEVICE, ascending inside [0, n_total]: frame f owns points [offsets[f], offsets[f+1]);
+ *               a frame whose pair is not ordered inside that range is treated as empty (checked on the device)
+ *   steps       [F][N][4][12] float64: per rigid step the rotation (row-major) and the translation
+ *   before      bit s set: step s translates before it rotates (the devkit: 0b1100)
+ *   intrinsics  [F][N][3][3] float64
+ * Geometry of the resample (stp3_depth_axis per image axis; configuration-only, built on the host as ATen builds its
+ * indices and weights -- stp3_amd.datas.DepthLabeller): the source rows / columns that are taps of a kept output row /
+ * column are numbered in ascending order ("slots");
+ *   tap      [n_out][2] int32   slots of i0 and i1 of every output index
+ *   weight   [n_out][2] float64 1 - lambda, lambda (for float32 maps: the float32 values, held in doubles)
+ *   slot_src [n_slot] int32     source index of a slot;   src_slot [n_src] int32  slot of a source index or -1
+ * An output map is [F][N][y.n_out][x.n_out]; out_kind chooses float32 / float64 values (integers, exact in both) or int64
+ * class ids  (int64)(min(max(v, d_lo), d_hi) - d_lo)  in float32 (the tables then describe the label rows and columns).
+ *
+ * stp3_depth_project            (a): pixels [n_total][N][2] int32 (u, v truncated; 0 where not kept), depth [n_total][N]
+ *                               float64 (the float32 z), keep [n_total][N] uint8
+ * stp3_depth_from_pixels        (b) + (c) on given pixels / depth / keep (the pinned entry)
+ * stp3_depth_from_lidar         (a) - (c) [- (d)]: winners by integer atomic max into the workspace
+ *                               (stp3_depth_workspace_bytes: the winner table, zeroed by the call, and 4 bytes per point
+ *                               and camera for the depths of the pairs that reached it)
+ * stp3_depth_labels_from_lidar  (a) - (d) in ONE launch without global scratch: a workgroup per image and band of label rows,
+ *                               winner table in LDS.  bands: at least that many bands (0: as few as fit);
+ *                               stp3_depth_labels_bands tells how many are used, STP3_EUNSUP if one label row's slots exceed LDS
+ * stp3_depth_from_maps          (c) [- (d)] of stored dense maps [F][N][y.n_src][x.n_src], float64 or float32 (map_dtype:
+ *                               STP3_DEPTH_OUT_F32 | _F64), arithmetic in the map's dtype
+ * All entries only enqueue on `stream`, allocate nothing and are deterministic (no floating-point atomics). */
+#define STP3_DEPTH_OUT_F32 0
+#define STP3_DEPTH_OUT_F64 1
+#define STP3_DEPTH_OUT_LABELS 2
+
+typedef struct stp3_depth_axis {
+    const int32_t* tap;
+    const double* weight;
+    const int32_t* slot_src;
+    const int32_t* src_slot;
+    int32_t n_out, n_slot, n_src, reserved;
+} stp3_depth_axis;
+
+typedef struct stp3_depth_dims {
+    int32_t F, N, n_total, out_kind;
+    float d_lo, d_hi;
+    stp3_depth_axis y, x;
+} stp3_depth_dims;
+
+int stp3_depth_project(int32_t F, int32_t N, int32_t n_total, int32_t H, int32_t W, const float* points,
+                       const int32_t* offsets, const double* steps, int32_t before, const double* intrinsics,
+                       int32_t* pixels, double* depth, uint8_t* keep, void* stream);
+int stp3_depth_workspace_bytes(const stp3_depth_dims* dims, size_t* bytes);
+int stp3_depth_from_pixels(const stp3_depth_dims* dims, const int32_t* pixels, const double* depth, const uint8_t* keep,
+                           const int32_t* offsets, void* workspace, size_t workspace_bytes, void* out, void* stream);
+int stp3_depth_from_lidar(const stp3_depth_dims* dims, const float* points, const int32_t* offsets, const double* steps,
+                          int32_t before, const double* intrinsics, void* workspace, size_t workspace_bytes, void* out,
+                          void* stream);
+int stp3_depth_labels_bands(const stp3_depth_dims* dims, int32_t bands, int32_t* used);
+int stp3_depth_labels_from_lidar(const stp3_depth_dims* dims, const float* points, const int32_t* offsets,
+                                 const double* steps, int32_t before, const double* intrinsics, int32_t bands,
+                                 int64_t* labels, void* stream);
+int stp3_depth_from_maps(const stp3_depth_dims* dims, const void* maps, int32_t map_dtype, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

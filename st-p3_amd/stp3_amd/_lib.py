@@ -158,6 +158,18 @@ class Poly(ctypes.Structure):
                 ('xy', ctypes.c_int32 * 16)]
 
 
+class DepthAxis(ctypes.Structure):
+    """struct stp3_depth_axis (include/stp3_hip.h)."""
+    _fields_ = ([(k, ctypes.c_void_p) for k in ('tap', 'weight', 'slot_src', 'src_slot')] +
+                [(k, ctypes.c_int32) for k in ('n_out', 'n_slot', 'n_src', 'reserved')])
+
+
+class DepthDims(ctypes.Structure):
+    """struct stp3_depth_dims (include/stp3_hip.h)."""
+    _fields_ = ([(k, ctypes.c_int32) for k in ('F', 'N', 'n_total', 'out_kind')] +
+                [('d_lo', ctypes.c_float), ('d_hi', ctypes.c_float), ('y', DepthAxis), ('x', DepthAxis)])
+
+
 class OptimBucket(ctypes.Structure):
     """struct stp3_optim_bucket (include/stp3_hip.h)."""
     _fields_ = [('grad', ctypes.c_void_p), ('param', ctypes.c_void_p), ('exp_avg', ctypes.c_void_p),
@@ -166,6 +178,7 @@ class OptimBucket(ctypes.Structure):
 
 DTYPE_F32 = 0
 DTYPE_BF16 = 1
+DEPTH_OUT_F32, DEPTH_OUT_F64, DEPTH_OUT_LABELS = 0, 1, 2
 
 VOX_REFERENCE = 0
 VOX_PIXELMAJOR = 1
@@ -293,6 +306,15 @@ SIGNATURES = {
     'stp3_instance_labels_workspace_bytes': (c_int, [c_int32, c_int32, ctypes.POINTER(c_size_t)]),
     'stp3_instance_labels': (c_int, [c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                      c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'stp3_depth_project': (c_int, [c_int32] * 5 + [c_void_p] * 3 + [c_int32] + [c_void_p] * 5),
+    'stp3_depth_workspace_bytes': (c_int, [ctypes.POINTER(DepthDims), ctypes.POINTER(c_size_t)]),
+    'stp3_depth_from_pixels': (c_int, [ctypes.POINTER(DepthDims)] + [c_void_p] * 5 + [c_size_t, c_void_p, c_void_p]),
+    'stp3_depth_from_lidar': (c_int, [ctypes.POINTER(DepthDims)] + [c_void_p] * 3 + [c_int32] + [c_void_p] * 2 +
+                              [c_size_t, c_void_p, c_void_p]),
+    'stp3_depth_labels_bands': (c_int, [ctypes.POINTER(DepthDims), c_int32, ctypes.POINTER(c_int32)]),
+    'stp3_depth_labels_from_lidar': (c_int, [ctypes.POINTER(DepthDims)] + [c_void_p] * 3 + [c_int32, c_void_p, c_int32,
+                                                                                         c_void_p, c_void_p]),
+    'stp3_depth_from_maps': (c_int, [ctypes.POINTER(DepthDims), c_void_p, c_int32, c_void_p, c_void_p]),
     'stp3_voxels_sum_fwd': (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     'stp3_voxels_sum_bwd': (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     'stp3_bn_eval_coefs': (c_int, [c_void_p, c_int32, ctypes.c_int64, c_void_p]),

@@ -457,3 +457,339 @@ def assemble_sample(frames, receptive_field, num_instances, planning=None, gt_de
         data['instance'], data['future_egomotion'], num_instances, ignore_index=ignore_index, subtract_egomotion=True,
         spatial_extent=spatial_extent)
     return data
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Depth labels (LIFT.GT_DEPTH): batch['depths'] from the LiDAR sweep or from stored maps.
+#   (a) projection    NuScenesExplorer.map_pointcloud_to_image of the nuScenes devkit: third-party, restated from its
+#                     published source, PARITY UNPINNED (csrc/stp3_depth.hip states the arithmetic this project defines)
+#   (b) scatter       NuscenesData.get_depth_from_lidar (NuscenesData.py:291-293): last point of a pixel wins
+#   (c) resample      :294-299 and get_input_data :261-266: bilinear, align_corners=False, crop, round half to even
+#   (d) class ids     trainer.py:269-276
+# ----------------------------------------------------------------------------------------------------------------------
+DEVKIT_BEFORE = (False, False, True, True)          # map_pointcloud_to_image: steps 3 and 4 translate, then rotate
+
+
+def depth_resample_axis(n_src, scale, out_index, dtype=np.float64):
+    """Taps and weights of ``F.interpolate(scale_factor=scale, mode='bilinear', align_corners=False)`` along one axis for
+    the output indices ``out_index``, as ATen builds them in the map's dtype (UpSampleKernel.cpp: source =
+    max(0, (1 / scale) (o + 0.5) - 0.5), i0 = min(trunc, n - 1), i1 = min(i0 + 1, n - 1), lambda = source - i0 in [0, 1]),
+    and the numbering of the source indices that are taps ("slots", ascending).  Returns a dict of numpy arrays: tap
+    (n_out, 2) int32 slots, weight (n_out, 2) float64 holding the ``dtype`` values, slot_src (n_slot,), src_slot (n_src,)."""
+    t = np.dtype(dtype).type
+    o = np.asarray(out_index, dtype=np.int64).astype(t)
+    src = np.maximum(t(1.0 / scale) * (o + t(0.5)) - t(0.5), t(0.0))
+    i0 = np.minimum(src.astype(np.int64), n_src - 1)
+    i1 = np.minimum(i0 + 1, n_src - 1)
+    lam = np.clip(src - i0.astype(t), t(0.0), t(1.0))
+    slot_src = np.unique(np.concatenate([i0, i1]))
+    src_slot = np.full(n_src, -1, dtype=np.int32)
+    src_slot[slot_src] = np.arange(len(slot_src), dtype=np.int32)
+    return {'tap': np.stack([src_slot[i0], src_slot[i1]], axis=1).astype(np.int32),
+            'weight': np.stack([t(1.0) - lam, lam], axis=1).astype(np.float64),
+            'slot_src': slot_src.astype(np.int32), 'src_slot': src_slot}
+
+
+class DepthLabeller:
+    """``NuscenesData.get_depth_from_lidar`` / the depth branch of ``get_input_data`` and the trainer's class ids, for
+    all frames and cameras of a batch.
+
+        lab = DepthLabeller(cfg)      # or source_hw=, scale=, crop=(left, top, right, bottom), downsample=, d_bound=
+        pixels, depth, keep = lab.project(points, offsets, steps, before, intrinsics)       # (a)
+        depths = lab.from_pixels(pixels, depth, keep, offsets)                              # (b) + (c): (F, N, Ho, Wo)
+        depths = lab.from_lidar(points, offsets, steps, before, intrinsics)                 # (a) - (c) fused
+        labels = lab.from_lidar(points, offsets, steps, before, intrinsics, labels=True)    # (a) - (d): (F, N, fH, fW) int64
+        depths = lab.from_maps(maps)                                                        # (c) of stored (F, N, H, W) maps
+        labels = lab.class_ids(depths)                                                      # (d)
+
+    points (n, 3) float32: the sweeps of the F frames one after the other, offsets (F + 1,) int32 their boundaries;
+    steps (F, N, 4, 12) float64: rotation (row-major) and translation of the four rigid steps; before: per step whether it
+    translates before it rotates (``DEVKIT_BEFORE``); intrinsics (F, N, 3, 3) float64.  ``depths`` is float32 by default
+    (``out_dtype=torch.float64`` on request; the values are integers): a frame's slice ``depths[f:f + 1]`` is the
+    ``depths`` entry ``assemble_sample(gt_depth=True)`` takes.  GPU tensors run csrc/stp3_depth.hip, CPU tensors the
+    ``reference_*`` methods -- the same statements with torch operators, which also run on GPU tensors."""
+
+    def __init__(self, cfg=None, source_hw=None, scale=None, crop=None, downsample=None, d_bound=None):
+        if cfg is not None:
+            p = get_resizing_and_cropping_parameters(cfg)
+            source_hw = (cfg.IMAGE.ORIGINAL_HEIGHT, cfg.IMAGE.ORIGINAL_WIDTH)
+            scale, crop = cfg.IMAGE.RESIZE_SCALE, p['crop']
+            downsample, d_bound = cfg.MODEL.ENCODER.DOWNSAMPLE, tuple(cfg.LIFT.D_BOUND)
+        self.source_hw, self.scale, self.crop = (int(source_hw[0]), int(source_hw[1])), float(scale), tuple(int(c) for c in crop)
+        self.downsample, self.d_bound = int(downsample), tuple(float(b) for b in d_bound)
+        h, w = self.source_hw
+        left, top, right, bottom = self.crop
+        hr, wr = int(math.floor(h * self.scale)), int(math.floor(w * self.scale))            # F.interpolate's output size
+        if min(left, top) < 0 or self.downsample < 1 or h < 3 or w < 3:
+            raise ValueError('DepthLabeller: negative crop origin, downsample < 1 or a source below 3 x 3')
+        self.rows, self.cols = np.arange(top, min(bottom, hr)), np.arange(left, min(right, wr))   # a slice clips
+        if len(self.rows) < 1 or len(self.cols) < 1:
+            raise ValueError('DepthLabeller: the crop window lies outside the resized map')
+        self.out_hw = (len(self.rows), len(self.cols))
+        self.label_hw = (len(self.rows[::self.downsample]), len(self.cols[::self.downsample]))
+        self._axes, self._device_axes = {}, {}
+        self.label_bands = 0                         # labels-only kernel: at least this many bands of label rows per image
+
+    # ---- configuration-only tables -----------------------------------------------------------------------------------
+    def axes(self, labels, dtype=np.float64):
+        """(rows' table, columns' table) of ``depth_resample_axis`` for the full map or for the label rows / columns."""
+        key = (bool(labels), np.dtype(dtype).name)
+        if key not in self._axes:
+            step = self.downsample if labels else 1
+            self._axes[key] = (depth_resample_axis(self.source_hw[0], self.scale, self.rows[::step], dtype),
+                               depth_resample_axis(self.source_hw[1], self.scale, self.cols[::step], dtype))
+        return self._axes[key]
+
+    def _tables(self, labels, dtype, device):
+        key = (bool(labels), np.dtype(dtype).name, str(device))
+        if key not in self._device_axes:
+            self._device_axes[key] = tuple({k: torch.from_numpy(v).to(device).contiguous() for k, v in ax.items()}
+                                           for ax in self.axes(labels, dtype))
+        return self._device_axes[key]
+
+    def class_ids(self, depths):
+        """trainer.py:269-276: every ``downsample``-th row and column, clamp(D_BOUND[0], D_BOUND[1] - 1) - D_BOUND[0], int64."""
+        ds = self.downsample
+        return self._clamp(depths[..., ::ds, ::ds])
+
+    def _clamp(self, depths):
+        return (torch.clamp(depths, self.d_bound[0], self.d_bound[1] - 1) - self.d_bound[0]).long().contiguous()
+
+    # ---- validation ----------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _before_mask(before):
+        before = [bool(b) for b in before]
+        if len(before) != 4:
+            raise ValueError('before: one flag per rigid step (4)')
+        return sum(1 << s for s, b in enumerate(before) if b)
+
+    @staticmethod
+    def _check_offsets(offsets, n_total, check):
+        if offsets.dim() != 1 or offsets.numel() < 2 or offsets.dtype != torch.int32:
+            raise ValueError('offsets: (F + 1,) int32')
+        if check:
+            o = offsets.detach().cpu().long()
+            if int(o[0]) < 0 or int(o[-1]) > n_total or bool((o[1:] < o[:-1]).any()):
+                raise ValueError('offsets: not ascending inside [0, number of points]')
+        return offsets.numel() - 1
+
+    def _check_cloud(self, points, offsets, steps, intrinsics, check):
+        if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+            raise ValueError('points: (n, 3) float32')
+        f = self._check_offsets(offsets, points.shape[0], check)
+        if steps.dim() != 4 or steps.shape[0] != f or tuple(steps.shape[2:]) != (4, 12) or steps.dtype != torch.float64:
+            raise ValueError('steps: (F, N, 4, 12) float64')
+        n = steps.shape[1]
+        if tuple(intrinsics.shape) != (f, n, 3, 3) or intrinsics.dtype != torch.float64:
+            raise ValueError('intrinsics: (F, N, 3, 3) float64')
+        if len({t.device for t in (points, offsets, steps, intrinsics)}) != 1:
+            raise ValueError('points, offsets, steps and intrinsics live on different devices')
+        return f, n
+
+    def _check_pixels(self, pixels, depth, keep, offsets, check):
+        n_total = pixels.shape[0]
+        if pixels.dim() != 3 or pixels.shape[2] != 2 or pixels.dtype != torch.int32:
+            raise ValueError('pixels: (n, N, 2) int32')
+        n = pixels.shape[1]
+        if tuple(depth.shape) != (n_total, n) or depth.dtype != torch.float64:
+            raise ValueError('depth: (n, N) float64')
+        if tuple(keep.shape) != (n_total, n) or keep.dtype != torch.bool:
+            raise ValueError('keep: (n, N) bool')
+        if len({t.device for t in (pixels, depth, keep, offsets)}) != 1:
+            raise ValueError('pixels, depth, keep and offsets live on different devices')
+        return self._check_offsets(offsets, n_total, check), n
+
+    @staticmethod
+    def _out_dtype(labels, out_dtype):
+        if labels:
+            return torch.int64, _lib.DEPTH_OUT_LABELS
+        if out_dtype not in (torch.float32, torch.float64):
+            raise ValueError('out_dtype: torch.float32 or torch.float64')
+        return out_dtype, (_lib.DEPTH_OUT_F32 if out_dtype == torch.float32 else _lib.DEPTH_OUT_F64)
+
+    # ---- the torch statements ------------------------------------------------------------------------------------------
+    @staticmethod
+    def _frames(offsets, n_total):
+        """(frame of every point clamped to a valid index, its index inside the frame, whether a frame owns it)."""
+        o = offsets.long()
+        p = torch.arange(n_total, device=offsets.device)
+        frame = torch.bucketize(p, o[1:].contiguous(), right=True)
+        owned = (frame < o.numel() - 1) & (p >= o[0])
+        frame = frame.clamp(max=o.numel() - 2)
+        return frame, p - o[frame], owned
+
+    def reference_project(self, points, offsets, steps, before, intrinsics):
+        """(a) in elementwise torch statements (no matmul: its summation order is the BLAS's)."""
+        self._check_cloud(points, offsets, steps, intrinsics, not points.is_cuda)
+        mask = self._before_mask(before)
+        h, w = self.source_hw
+        frame, _, owned = self._frames(offsets, points.shape[0])
+        st, k = steps[frame], intrinsics[frame]                                              # (n, N, 4, 12), (n, N, 3, 3)
+        x, y, z = (points[:, i:i + 1].expand(-1, steps.shape[1]) for i in range(3))
+        for s in range(4):
+            r = st[:, :, s]
+            if (mask >> s) & 1:
+                x, y, z = ((x.double() + r[..., 9]).float(), (y.double() + r[..., 10]).float(), (z.double() + r[..., 11]).float())
+            dx, dy, dz = x.double(), y.double(), z.double()
+            x = (r[..., 0] * dx + r[..., 1] * dy + r[..., 2] * dz).float()
+            y = (r[..., 3] * dx + r[..., 4] * dy + r[..., 5] * dz).float()
+            z = (r[..., 6] * dx + r[..., 7] * dy + r[..., 8] * dz).float()
+            if not (mask >> s) & 1:
+                x, y, z = ((x.double() + r[..., 9]).float(), (y.double() + r[..., 10]).float(), (z.double() + r[..., 11]).float())
+        dx, dy, dz = x.double(), y.double(), z.double()
+        p0 = k[..., 0, 0] * dx + k[..., 0, 1] * dy + k[..., 0, 2] * dz
+        p1 = k[..., 1, 0] * dx + k[..., 1, 1] * dy + k[..., 1, 2] * dz
+        p2 = k[..., 2, 0] * dx + k[..., 2, 1] * dy + k[..., 2, 2] * dz
+        u, v = p0 / p2, p1 / p2
+        keep = (z > 1.0) & (u > 1.0) & (u < float(w - 1)) & (v > 1.0) & (v < float(h - 1)) & owned[:, None]
+        zero = torch.zeros((), dtype=torch.float64, device=points.device)
+        pixels = torch.stack([torch.where(keep, u, zero), torch.where(keep, v, zero)], dim=-1).to(torch.int32)   # toward zero
+        return pixels, torch.where(owned[:, None], dz, zero), keep
+
+    @staticmethod
+    def _blend(tab, ay, ax, dtype):
+        """hy0 (wx0 A + wx1 B) + hy1 (wx0 C + wx1 D) of a (..., n_slot_y, n_slot_x) table, rounded half to even."""
+        ty, tx = ay['tap'].long(), ax['tap'].long()
+        hy, wx = ay['weight'].to(dtype), ax['weight'].to(dtype)
+        top, bot = tab[..., ty[:, 0], :], tab[..., ty[:, 1], :]
+        a, b, c, d = top[..., tx[:, 0]], top[..., tx[:, 1]], bot[..., tx[:, 0]], bot[..., tx[:, 1]]
+        hy0, hy1, wx0, wx1 = hy[:, 0:1], hy[:, 1:2], wx[:, 0], wx[:, 1]
+        return torch.round(hy0 * (wx0 * a + wx1 * b) + hy1 * (wx0 * c + wx1 * d))
+
+    def reference_from_pixels(self, pixels, depth, keep, offsets, labels=False, out_dtype=torch.float32):
+        """(b) + (c) [+ (d)]: the winner of a source pixel is the highest point index (an integer amax: deterministic on
+        every device), taken only where the pixel is a tap of a kept output (with ``labels``: of a label's row and column);
+        then the four-tap blend in float64."""
+        f, n = self._check_pixels(pixels, depth, keep, offsets, not pixels.is_cuda)
+        dev = pixels.device
+        ay, ax = self._tables(labels, np.float64, dev)
+        nsy, nsx = ay['slot_src'].numel(), ax['slot_src'].numel()
+        h, w = self.source_hw
+        frame, local, owned = self._frames(offsets, pixels.shape[0])
+        px, py = pixels[..., 0].long(), pixels[..., 1].long()
+        inside = keep & owned[:, None] & (px >= 0) & (px < w) & (py >= 0) & (py < h)
+        sx, sy = ax['src_slot'].long()[px.clamp(0, w - 1)], ay['src_slot'].long()[py.clamp(0, h - 1)]
+        ok = inside & (sx >= 0) & (sy >= 0)
+        cam = torch.arange(n, device=dev)
+        lin = ((frame[:, None] * n + cam[None]) * nsy + sy) * nsx + sx
+        win = torch.zeros(f * n * nsy * nsx, dtype=torch.int64, device=dev)
+        win.scatter_reduce_(0, torch.where(ok, lin, torch.zeros_like(lin)).reshape(-1),
+                            torch.where(ok, (local + 1)[:, None].expand_as(lin), torch.zeros_like(lin)).reshape(-1), 'amax')
+        win = win.view(f, n, nsy, nsx)
+        point = offsets.long()[:-1].view(f, 1, 1, 1) + win - 1
+        flat = depth.reshape(-1)
+        if flat.numel() == 0:
+            tab = torch.zeros(f, n, nsy, nsx, dtype=torch.float64, device=dev)
+        else:
+            tab = torch.where(win > 0, flat[(point.clamp(0, pixels.shape[0] - 1) * n + cam.view(1, n, 1, 1))],
+                              torch.zeros((), dtype=torch.float64, device=dev))
+        out = self._blend(tab, ay, ax, torch.float64)
+        return self._clamp(out.float()) if labels else out.to(out_dtype)
+
+    def reference_from_lidar(self, points, offsets, steps, before, intrinsics, labels=False, out_dtype=torch.float32):
+        pixels, depth, keep = self.reference_project(points, offsets, steps, before, intrinsics)
+        return self.reference_from_pixels(pixels, depth, keep, offsets, labels, out_dtype)
+
+    def reference_from_maps(self, maps, labels=False, out_dtype=torch.float32):
+        """(c) [+ (d)] of stored maps (F, N, H, W), float64 or float32, in the maps' dtype."""
+        self._check_maps(maps)
+        ay, ax = self._tables(labels, np.float64 if maps.dtype == torch.float64 else np.float32, maps.device)
+        tab = maps[..., ay['slot_src'].long(), :][..., ax['slot_src'].long()]
+        out = self._blend(tab, ay, ax, maps.dtype)
+        return self._clamp(out.float()) if labels else out.to(out_dtype)
+
+    def _check_maps(self, maps):
+        if maps.dim() != 4 or tuple(maps.shape[2:]) != self.source_hw or maps.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f'maps: (F, N, {self.source_hw[0]}, {self.source_hw[1]}) float64 or float32')
+
+    # ---- the kernels ---------------------------------------------------------------------------------------------------
+    def _dims(self, f, n, n_total, labels, out_kind, dtype, device):
+        ay, ax = self._tables(labels, dtype, device)
+        d = _lib.DepthDims()
+        d.F, d.N, d.n_total, d.out_kind = f, n, n_total, out_kind
+        d.d_lo, d.d_hi = self.d_bound[0], self.d_bound[1] - 1                  # (ctypes rounds to float32, as torch.clamp)
+        for axis, t, n_src in ((d.y, ay, self.source_hw[0]), (d.x, ax, self.source_hw[1])):
+            axis.tap, axis.weight = t['tap'].data_ptr(), t['weight'].data_ptr()
+            axis.slot_src, axis.src_slot = t['slot_src'].data_ptr(), t['src_slot'].data_ptr()
+            axis.n_out, axis.n_slot, axis.n_src = t['tap'].shape[0], t['slot_src'].numel(), n_src
+        return d
+
+    def _workspace(self, d, device):
+        need = ctypes.c_size_t()
+        _lib.check(_lib.lib().stp3_depth_workspace_bytes(ctypes.byref(d), ctypes.byref(need)), 'stp3_depth_workspace_bytes')
+        return torch.empty(max(need.value, 16), dtype=torch.uint8, device=device), need.value
+
+    def project(self, points, offsets, steps, before, intrinsics, check=False):
+        """(a): pixels (n, N, 2) int32 = (u, v) truncated toward zero (0 where not kept), depth (n, N) float64 (the
+        float32 z), keep (n, N) bool."""
+        if not points.is_cuda:
+            return self.reference_project(points, offsets, steps, before, intrinsics)
+        f, n = self._check_cloud(points, offsets, steps, intrinsics, check)
+        dev, n_total = points.device, points.shape[0]
+        points, offsets, steps, intrinsics = (t.contiguous() for t in (points, offsets, steps, intrinsics))
+        pixels = torch.empty(n_total, n, 2, dtype=torch.int32, device=dev)
+        depth = torch.empty(n_total, n, dtype=torch.float64, device=dev)
+        keep = torch.empty(n_total, n, dtype=torch.uint8, device=dev)
+        _lib.check(_lib.lib().stp3_depth_project(f, n, n_total, self.source_hw[0], self.source_hw[1], ops._ptr(points),
+                                                 ops._ptr(offsets), ops._ptr(steps), self._before_mask(before),
+                                                 ops._ptr(intrinsics), ops._ptr(pixels), ops._ptr(depth), ops._ptr(keep),
+                                                 ops._stream()), 'stp3_depth_project')
+        return pixels, depth, keep.view(torch.bool)
+
+    def from_pixels(self, pixels, depth, keep, offsets, labels=False, out_dtype=torch.float32, check=False):
+        """(b) + (c) [+ (d)] of projected points: depths (F, N, Ho, Wo), or int64 class ids (F, N, fH, fW)."""
+        if not pixels.is_cuda:
+            return self.reference_from_pixels(pixels, depth, keep, offsets, labels, out_dtype)
+        f, n = self._check_pixels(pixels, depth, keep, offsets, check)
+        dev = pixels.device
+        dtype, kind = self._out_dtype(labels, out_dtype)
+        d = self._dims(f, n, pixels.shape[0], labels, kind, np.float64, dev)
+        pixels, depth, keep, offsets = (t.contiguous() for t in (pixels, depth, keep, offsets))
+        ws, nbytes = self._workspace(d, dev)
+        out = torch.empty(f, n, d.y.n_out, d.x.n_out, dtype=dtype, device=dev)
+        _lib.check(_lib.lib().stp3_depth_from_pixels(ctypes.byref(d), ops._ptr(pixels), ops._ptr(depth),
+                                                     ops._ptr(keep.view(torch.uint8)), ops._ptr(offsets), ops._ptr(ws), nbytes,
+                                                     ops._ptr(out), ops._stream()), 'stp3_depth_from_pixels')
+        return out
+
+    def from_lidar(self, points, offsets, steps, before, intrinsics, labels=False, out_dtype=torch.float32, check=False,
+                   fused=False):
+        """(a) - (c) [- (d)] from the sweeps.  ``labels=True``: int64 class ids (F, N, fH, fW), equal to
+        ``class_ids(from_lidar(...))``, through the winner table of the label rows and columns in global memory like the
+        full map (the default: measured faster at the trained shape); with ``fused`` in one launch
+        that keeps the winners of an image in LDS and needs no scratch."""
+        if not points.is_cuda:
+            return self.reference_from_lidar(points, offsets, steps, before, intrinsics, labels, out_dtype)
+        f, n = self._check_cloud(points, offsets, steps, intrinsics, check)
+        dev = points.device
+        dtype, kind = self._out_dtype(labels, out_dtype)
+        d = self._dims(f, n, points.shape[0], labels, kind, np.float64, dev)
+        points, offsets, steps, intrinsics = (t.contiguous() for t in (points, offsets, steps, intrinsics))
+        mask = self._before_mask(before)
+        out = torch.empty(f, n, d.y.n_out, d.x.n_out, dtype=dtype, device=dev)
+        lib = _lib.lib()
+        if labels and fused:
+            _lib.check(lib.stp3_depth_labels_from_lidar(ctypes.byref(d), ops._ptr(points), ops._ptr(offsets), ops._ptr(steps),
+                                                        mask, ops._ptr(intrinsics), self.label_bands, ops._ptr(out),
+                                                        ops._stream()), 'stp3_depth_labels_from_lidar')
+            return out
+        ws, nbytes = self._workspace(d, dev)
+        _lib.check(lib.stp3_depth_from_lidar(ctypes.byref(d), ops._ptr(points), ops._ptr(offsets), ops._ptr(steps), mask,
+                                             ops._ptr(intrinsics), ops._ptr(ws), nbytes, ops._ptr(out), ops._stream()),
+                   'stp3_depth_from_lidar')
+        return out
+
+    def from_maps(self, maps, labels=False, out_dtype=torch.float32):
+        """(c) [- (d)] of stored dense maps (F, N, H, W), float64 or float32, arithmetic in the maps' dtype."""
+        if not maps.is_cuda:
+            return self.reference_from_maps(maps, labels, out_dtype)
+        self._check_maps(maps)
+        dtype, kind = self._out_dtype(labels, out_dtype)
+        f, n = maps.shape[:2]
+        is64 = maps.dtype == torch.float64
+        d = self._dims(f, n, 0, labels, kind, np.float64 if is64 else np.float32, maps.device)
+        maps = maps.contiguous()
+        out = torch.empty(f, n, d.y.n_out, d.x.n_out, dtype=dtype, device=maps.device)
+        _lib.check(_lib.lib().stp3_depth_from_maps(ctypes.byref(d), ops._ptr(maps), _lib.DEPTH_OUT_F64 if is64 else
+                                                   _lib.DEPTH_OUT_F32, ops._ptr(out), ops._stream()), 'stp3_depth_from_maps')
+        return out
