@@ -925,6 +925,89 @@ int stp3_instance_track(int32_t B, int32_t S, int32_t H, int32_t W, float matchi
                         const float* flow, int32_t* out, int32_t* err, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Evaluation scorer (csrc/stp3_eval.hip) -- the metric updates of the reference's evaluation loop, evaluate.py:95-137, as
+ * launches on the caller's stream with nothing in them that waits for the host: a hipGraph can hold them.  The states are
+ * ADDED TO, never overwritten; the caller zeroes them (and `err`) once.  The host side: st-p3_amd/stp3_amd/evaluation.py.
+ *
+ * stp3_eval_semantic -- evaluate.py:95-119 (argmax of every semantic head) and IntersectionOverUnion.update
+ * (stp3/metrics.py:37-43, stat_scores_multiple_classes) for all heads of an update in ONE launch.
+ *   segmentation [B][S][Cs][H][W], pedestrian [B][S][Cp][H][W] (Cp = 0: NULL), hdmap [B][2 E][H][W] (E = 0: NULL): logits,
+ *                float32 or bf16, any non-negative element strides (channels-last included)
+ *   segmentation_label, pedestrian_label [B][S][1][H][W], hdmap_label [B][E][H][W]: int64, dense
+ *   counts       int64 [2 + E][n_classes][4]: tp, fp, fn, support per class of the heads segmentation, pedestrian (left alone
+ *                when Cp = 0), hd-map element 0 .. E - 1 (the logit pair 2 e, 2 e + 1)
+ *   Frames first .. S - 1 of the two temporal heads are scored; the hd-map has no time axis.  Per pixel: the arg-max class
+ *   (the first maximal class wins a tie, a NaN counts as the maximum: torch.argmax, the rule of stp3_plan_scene); class c
+ *   counts tp when prediction and label are both c, fp when only the prediction is, fn when only the label is, support
+ *   when the label is.  A label (or prediction) outside [0, n_classes), such as 255, is no class of its own but still makes
+ *   the other side's class a false positive / negative.  Integer sums: exact and the same in every run.
+ * STP3_EINVAL: a null pointer (a head that is switched off excepted, and then required to be NULL), a size < 1, first
+ * outside [0, S); STP3_EUNSUP: Cs or Cp > 16, n_classes > 8, H or W > 1024, another dtype, a stride of 2^31 elements or
+ * more, more than 65 535 planes (B (S - first) per temporal head + B E).
+ *
+ * stp3_eval_planning -- PlanningMetric.update (stp3/metrics.py:292-389; evaluate.py:122-137) in one launch of one workgroup.
+ *   trajs, gt_trajs [B][T][>= 2] float32 (lateral, forward, ...), sample and point strides in floats
+ *   the label maps of stp3_eval_semantic ([B][S][1][H][W] int64; pedestrian_label may be NULL): the true occupancy of step t
+ *   is `segmentation label != 0 or pedestrian label != 0` at frame first_future + t, evaluated where it is read
+ *   footprint [K][2] int32: the (row, column) cell offsets of the ego box (cost.BaseCost.footprint(0))
+ *   obj_col, obj_box_col int64 [T], total int64 [1], l2 float64 [T]
+ *   Per step, in float32 without contraction: distance = sqrtf(dx dx + dy dy); x is negated (the BEV flip); a box cell is
+ *   trunc(y / dx0 + row) / trunc(x / dx1 + column) clamped into the grid; the point's cell trunc((y - bx0) / dx0),
+ *   trunc((x - bx1) / dx1) counts only inside the grid; steps at which the EXPERT's box collides are not counted.  The
+ *   distances are added to l2 in ascending sample order by one thread per step; total += B.
+ * STP3_EINVAL: a null pointer (pedestrian_label excepted), a size < 1, first_future < 0 or first_future + T > S, a cell size
+ * <= 0, a negative stride; STP3_EUNSUP: B T > 1024, H or W > 1024.
+ *
+ * stp3_eval_panoptic -- PanopticMetric.update (stp3/metrics.py:94-261) for n_classes = 2, vehicles_id = 1: one workgroup per
+ * sample with the loop over its frames inside, then a one-workgroup launch that finishes.
+ *   pred, gt   [B][S][H][W] int32 (wide_ids = 0) or int64 (wide_ids != 0) instance ids, 0 = background; frames first .. S - 1
+ *   workspace  stp3_eval_panoptic_workspace_bytes: the per-frame results [B (S - first)][4][2] float32 (iou, true positive,
+ *              false positive, false negative; class 0 = background, 1 = vehicle) stay there for the caller to read
+ *   state      float32 [4][2]
+ *   err        [4] int32, zeroed by the caller: word k is set to 1 when  0: an id lies outside [0, 2^20) (the pixel counts as
+ *              background),  1: no ground-truth pixel of the update is background,  2: a frame has more distinct (gt id,
+ *              predicted id) pairs than the table holds -- STP3_EVAL_PANOPTIC_PAIRS - 1 besides (background, background) --
+ *              or a sample matched more than STP3_EVAL_PANOPTIC_PAIRS distinct gt ids (the frame's result is then
+ *              meaningless);  3: reserved, never set.  The kernels always run to their end.
+ *   Per frame: the distinct pairs with their pixel counts and the areas per id; in ascending (gt id, predicted id): IoU =
+ *   (n + 1e-9f) / (area_gt + area_pred - n + 1e-9f) in float32; a match needs IoU > 0.5 and both sides background or both
+ *   vehicles; with temporally_consistent != 0 a matched vehicle whose gt id was last matched (in an earlier frame of the
+ *   sample) to ANOTHER predicted id counts as one false negative plus one false positive instead; ids with pixels and no
+ *   match candidate count as false negative (gt) / false positive (predicted).  The frames are added in update order
+ *   (sample-major, frame ascending) into a zero total, which is added to `state`: one update of a zero state has the
+ *   reference's bits.
+ * STP3_EINVAL: a null pointer, a size < 1, first outside [0, S); STP3_EUNSUP: H or W > 1024, H W >= 2^24, B > 65 535;
+ * STP3_ENOSPACE: the workspace is too small.
+ * All are answered before anything touches the GPU. */
+#define STP3_EVAL_PANOPTIC_PAIRS 1024
+typedef struct stp3_eval_dims {
+    int32_t B, S, H, W;
+    int32_t Cs, Cp, E;                            /* classes of the two temporal heads (Cp = 0: none), hd-map elements */
+    int32_t n_classes;                            /* classes counted per head */
+    int32_t first;                                /* first frame scored: the model's receptive field - 1 */
+    int32_t seg_dtype, ped_dtype, hd_dtype;       /* STP3_DTYPE_* */
+    int64_t seg_stride[5], ped_stride[5];         /* elements: sample, frame, class, row, column */
+    int64_t hd_stride[4];                         /* elements: sample, channel, row, column */
+} stp3_eval_dims;
+int stp3_eval_semantic(const stp3_eval_dims* dims, const void* segmentation, const void* pedestrian, const void* hdmap,
+                       const int64_t* segmentation_label, const int64_t* pedestrian_label, const int64_t* hdmap_label,
+                       int64_t* counts, void* stream);
+typedef struct stp3_eval_plan_dims {
+    int32_t B, T, S, H, W;
+    int32_t K;                                    /* footprint cells */
+    int32_t first_future;                         /* frame of step 0: the model's receptive field */
+    float dx0, dx1, bx0, bx1;                     /* cell size and first cell centre, (forward, lateral) */
+    int64_t traj_stride[2], gt_stride[2];         /* floats: sample, point */
+} stp3_eval_plan_dims;
+int stp3_eval_planning(const stp3_eval_plan_dims* dims, const float* trajs, const float* gt_trajs,
+                       const int64_t* segmentation_label, const int64_t* pedestrian_label, const int32_t* footprint,
+                       int64_t* obj_col, int64_t* obj_box_col, int64_t* total, double* l2, void* stream);
+int stp3_eval_panoptic_workspace_bytes(int32_t B, int32_t S, int32_t first, size_t* bytes);
+int stp3_eval_panoptic(int32_t B, int32_t S, int32_t H, int32_t W, int32_t first, int32_t temporally_consistent,
+                       int32_t wide_ids, const void* pred, const void* gt, void* workspace, size_t workspace_bytes,
+                       float* state, int32_t* err, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Camera images: decoded bytes -> network input (csrc/stp3_image.hip).  The per-image chain of the reference's loader,
  * stp3/datas/NuscenesData.py:236-244: resize_and_crop_image (stp3/utils/geometry.py:9-13: PIL resize BILINEAR + crop)
  * followed by torchvision ToTensor + Normalize (:68-72), for all N images of a batch in one launch.

@@ -170,6 +170,20 @@ class DepthDims(ctypes.Structure):
                 [('d_lo', ctypes.c_float), ('d_hi', ctypes.c_float), ('y', DepthAxis), ('x', DepthAxis)])
 
 
+class EvalDims(ctypes.Structure):
+    """struct stp3_eval_dims (include/stp3_hip.h)."""
+    _fields_ = ([(k, ctypes.c_int32) for k in ('B', 'S', 'H', 'W', 'Cs', 'Cp', 'E', 'n_classes', 'first', 'seg_dtype', 'ped_dtype',
+                                               'hd_dtype')] +
+                [('seg_stride', ctypes.c_int64 * 5), ('ped_stride', ctypes.c_int64 * 5), ('hd_stride', ctypes.c_int64 * 4)])
+
+
+class EvalPlanDims(ctypes.Structure):
+    """struct stp3_eval_plan_dims (include/stp3_hip.h)."""
+    _fields_ = ([(k, ctypes.c_int32) for k in ('B', 'T', 'S', 'H', 'W', 'K', 'first_future')] +
+                [(k, ctypes.c_float) for k in ('dx0', 'dx1', 'bx0', 'bx1')] +
+                [('traj_stride', ctypes.c_int64 * 2), ('gt_stride', ctypes.c_int64 * 2)])
+
+
 class OptimBucket(ctypes.Structure):
     """struct stp3_optim_bucket (include/stp3_hip.h)."""
     _fields_ = [('grad', ctypes.c_void_p), ('param', ctypes.c_void_p), ('exp_avg', ctypes.c_void_p),
@@ -299,6 +313,10 @@ SIGNATURES = {
     'stp3_traj_sample': (c_int, [ctypes.POINTER(SamplerDims)] + [c_void_p] * 6),
     'stp3_instance_segment': (c_int, [c_int32] * 3 + [c_float] + [c_void_p] * 7),
     'stp3_instance_track': (c_int, [c_int32] * 4 + [c_float] + [c_void_p] * 5),
+    'stp3_eval_semantic': (c_int, [ctypes.POINTER(EvalDims)] + [c_void_p] * 8),
+    'stp3_eval_planning': (c_int, [ctypes.POINTER(EvalPlanDims)] + [c_void_p] * 10),
+    'stp3_eval_panoptic_workspace_bytes': (c_int, [c_int32] * 3 + [ctypes.POINTER(c_size_t)]),
+    'stp3_eval_panoptic': (c_int, [c_int32] * 7 + [c_void_p] * 3 + [c_size_t] + [c_void_p] * 3),
     'stp3_image_prep_rows_per_workgroup': (c_int, []),
     'stp3_image_prep_lds_bytes': (c_int, [ctypes.POINTER(ImageDims), c_int32, ctypes.POINTER(c_size_t)]),
     'stp3_image_prep': (c_int, [ctypes.POINTER(ImageDims)] + [c_void_p] * 5 + [c_int32, c_void_p, c_void_p]),
