@@ -503,7 +503,8 @@ int stp3_conv2d_wgrad(const stp3_conv_dims* dims, const void* dy, const void* x,
  * stp3_conv2d_wgrad_workspace(dims) bytes that must stay untouched until the reduction; *splits receives the split count.
  * stp3_conv2d_wgrad_reduce_batch sums the partials of n such layers in ONE launch per STP3_WGRAD_BATCH_MAX jobs (`jobs` is a
  * HOST array, it travels as the kernel argument): dw[i] = sum_k partials[k][i], the additions in the order of
- * stp3_conv2d_wgrad (bit-identical results). */
+ * stp3_conv2d_wgrad (bit-identical results).  pre_coef / pre_act: NULL / ignored, or the operand-side BatchNorm of
+ * stp3_conv2d_wgrad_pre (below). */
 #define STP3_WGRAD_BATCH_MAX 96
 typedef struct stp3_wgrad_job {
     const void* partials;   /* device: [splits][numel] float32 */
@@ -512,9 +513,24 @@ typedef struct stp3_wgrad_job {
     int32_t splits;
     int32_t reserved;
 } stp3_wgrad_job;
-int stp3_conv2d_wgrad_partials(const stp3_conv_dims* dims, const void* dy, const void* x, void* partials,
-                               size_t partials_bytes, int32_t* splits, void* stream);
+int stp3_conv2d_wgrad_partials(const stp3_conv_dims* dims, const void* dy, const void* x, const float* pre_coef,
+                               int32_t pre_act, void* partials, size_t partials_bytes, int32_t* splits, void* stream);
 int stp3_conv2d_wgrad_reduce_batch(int32_t n, const stp3_wgrad_job* jobs, void* stream);
+
+/* BatchNorm (+ ReLU) applied in the OPERAND LOAD of the 1x1 convolution behind it (csrc/stp3_conv.hip, PRE): for the chains
+ * conv -> BatchNorm -> ReLU -> 1x1 conv of stp3/layers/convolutions.py:183-280 (ASPP branches -> projection, DeepLabHead tail)
+ * and stp3/models/decoder.py:42-66 (the heads), whose normalised tensor has no reader but that 1x1 convolution.  x is the
+ * PRODUCER's convolution output z; the kernels use bf16(act(scale[ci] * z + shift[ci])) in its place -- bit for bit what
+ * stp3_bn_apply_fwd (training mode, no skip, no per-sample terms) would have stored -- so that tensor is neither written nor read:
+ *   stp3_conv2d_fwd_pre    stp3_conv2d_fwd (no statistics) of that operand; always the LDS-tiled kernel
+ *   stp3_conv2d_wgrad_pre  stp3_conv2d_wgrad of that operand (stp3_conv2d_wgrad_partials takes the same two arguments)
+ * pre_coef = [scale | shift][Cin] float32 (the first two rows stp3_bn_finalize writes), pre_act = STP3_ACT_NONE / STP3_ACT_RELU.
+ * Pieces that stand for padding (rows beyond N * H * W, the channel tail) reach the matrix cores as ZERO, after the transform.
+ * 1x1 / stride 1 / no padding, x and w each below 2 GiB, Cin <= 4096 (forward); anything else: STP3_EUNSUP. */
+int stp3_conv2d_fwd_pre(const stp3_conv_dims* dims, const void* x, const void* w, const float* bias, const float* pre_coef,
+                        int32_t pre_act, void* y, void* stream);
+int stp3_conv2d_wgrad_pre(const stp3_conv_dims* dims, const void* dy, const void* x, const float* pre_coef, int32_t pre_act,
+                          float* dw, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Squeeze-and-excitation data passes (csrc/stp3_se.hip).

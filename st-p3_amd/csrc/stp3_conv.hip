@@ -112,7 +112,31 @@ struct EpiArgs {
     int cvalid;                 // AFFINE: channels that exist; the lanes [cvalid, Cout) are written as zeros
     const float* sbias;         // AFFINE, tiled kernel: per-sample bias [N][cvalid] added in front of the BatchNorm (the pooled
     int hw;                     // branch of an ASPP projection), folded into the shift; hw = Ho * Wo output pixels per sample
+    const float* pre;           // PRE (tiled kernel, 1x1 layers): [scale | shift][Cin] of the BatchNorm in front of this convolution
+    int pre_off;                // ... and the byte offset of their LDS table behind the staging buffers / the epilogue tile
 };
+
+// Operand-side BatchNorm (+ ReLU).  A 1x1 convolution reads every element of its input once, so the apply pass of the
+// BatchNorm in front of it (bn_apply_fwd_kernel: read z, write y = act(scale * z + shift), read y again here) can happen in
+// the staging registers instead: the consumer reads z and the tensor y never exists.  The statement of bn_apply_fwd_kernel
+// (TRAIN, no skip, no per-sample terms) on one bf16 pair, operation for operation: same bits as the stored y.
+enum { kPreNone = 0, kPreAffine = 1, kPreRelu = 2 };
+template <int PRE>
+__device__ __forceinline__ uint32_t pre_pair(uint32_t wd, stp3_f32x2 cs, stp3_f32x2 ct) {
+    const stp3_f32x2 e0 = {__uint_as_float(wd << 16), __uint_as_float(wd & 0xffff0000u)};
+    stp3_f32x2 out = pk_fma(e0, cs, ct);
+    if (PRE == kPreRelu) out = stp3_f32x2{fmaxf(out.x, 0.f), fmaxf(out.y, 0.f)};
+    return pack_bf16(out.x, out.y);
+}
+// ... on a 16-byte piece (8 channels: constants cs / ct per pair); `mask` = all ones, or zero for a piece that stands for
+// padding (a row beyond the matrix, an out-of-range load): act(shift) is not zero, the matrix cores must still see zeros
+template <int PRE>
+__device__ __forceinline__ u32x4 pre_piece(u32x4 v, const stp3_f32x2 (&cs)[4], const stp3_f32x2 (&ct)[4], uint32_t mask) {
+    u32x4 o;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[r] = pre_pair<PRE>(v[r], cs[r], ct[r]) & mask;
+    return o;
+}
 
 template <int ACT>
 __device__ __forceinline__ float epi_act(float v) {
@@ -135,7 +159,10 @@ __device__ __forceinline__ float epi_act_grad(float pre) {
 // offset kBufOob of a padding tap / a row beyond the matrix -- instead of selecting between a 64-bit address and the address of
 // g_zero16 (which the compiler turned into exec-mask branches: 284 instructions per K step beside 16 MFMAs, 103 of them VALU
 // and 115 SALU, `s_getpc` of g_zero16 ten times per step).
-template <int BN, int MODE = kModePlain, int ACT = STP3_ACT_NONE, bool BUF = false>
+// PRE (kPreAffine / kPreRelu; 1x1, stride-1, unpadded layers): the pixel operand is act(scale[ci] * x + shift[ci]) rounded to bf16
+// (pre_pair), applied to the staged registers between the global load and the LDS store.  The constants of all input channels
+// sit in an LDS table, filled once per workgroup, zero for ci >= Cin; the pieces of rows beyond M are masked to zero.
+template <int BN, int MODE = kModePlain, int ACT = STP3_ACT_NONE, bool BUF = false, int PRE = kPreNone>
 __global__ __launch_bounds__(256) void conv2d_igemm_kernel(ConvDims d, int tiles_co, const uint16_t* __restrict__ x,
                                                            const uint16_t* __restrict__ w,
                                                            const float* __restrict__ bias, void* __restrict__ y,
@@ -161,9 +188,11 @@ __global__ __launch_bounds__(256) void conv2d_igemm_kernel(ConvDims d, int tiles
     const uint16_t* prow[4];                              // pixel rows: address of (hi0, wi0, channel 0), or `zero`
     uint32_t poff[4];                                     // BUF: the same as a byte offset from x (mod 2^32), kBufOob = no row
     int phi[4], pwi[4];                                   // ... and hi0, wi0
+    uint32_t rmask[4];                                    // PRE: all ones for a row of the matrix, zero beyond it
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int m = m0 + rr + 32 * i;
+        if (PRE) rmask[i] = m < d.M ? 0xffffffffu : 0u;
         if (m < d.M) {
             const int wo = m % d.Wo;
             const int t = m / d.Wo;
@@ -200,6 +229,19 @@ __global__ __launch_bounds__(256) void conv2d_igemm_kernel(ConvDims d, int tiles
     const bool pointwise = taps == 1 && d.pad_h == 0 && d.pad_w == 0 && (d.Ho - 1) * d.stride < d.H &&
                            (d.Wo - 1) * d.stride < d.W;
 
+    const int steps = (d.Ktot + kBK - 1) / kBK;
+    // PRE: [scale | shift][steps * 64] float32 in LDS, zero for the K tail (loads of the tail return zeros: 0 * 0 + 0)
+    float* const ptab = reinterpret_cast<float*>(smem + ep.pre_off);
+    const int kpad = steps * kBK;
+    int prek = 0;                                          // PRE: first channel of the piece(s) in flight
+    if (PRE) {
+        for (int e = tid; e < 2 * kpad; e += 256) {
+            const int h = e >= kpad, c = e - h * kpad;
+            ptab[e] = c < d.Cin ? ep.pre[h * d.Cin + c] : 0.f;
+        }
+        __syncthreads();
+    }
+
     u32x4 ra[4], rb[BN / 32];                              // first-class vectors: HIP's uint4 (a struct) ends up in scratch here
     auto load_step = [&]() {                               // the piece of the current (tap, ci) for every row of this thread
         const bool kvalid = tap < taps;
@@ -226,6 +268,7 @@ __global__ __launch_bounds__(256) void conv2d_igemm_kernel(ConvDims d, int tiles
             }
         }
         const int kk = tap * d.Cin + ci;
+        if (PRE) prek = kk;                                // (one tap: kk is the channel, < kpad)
 #pragma unroll
         for (int i = 0; i < BN / 32; ++i) {
             if (BUF) rb[i] = buffer_load16(wbuf, (kvalid & (woff[i] != kBufOob)) ? woff[i] + (uint32_t)kk * 2u : kBufOob);
@@ -240,6 +283,15 @@ __global__ __launch_bounds__(256) void conv2d_igemm_kernel(ConvDims d, int tiles
         }
     };
     auto store_step = [&](uint8_t* buf) {
+        if (PRE) {                                         // the loaded pixels -> what the BatchNorm apply pass would have stored
+            const f32x4 s0 = *reinterpret_cast<const f32x4*>(ptab + prek), s1 = *reinterpret_cast<const f32x4*>(ptab + prek + 4);
+            const f32x4 t0 = *reinterpret_cast<const f32x4*>(ptab + kpad + prek);
+            const f32x4 t1 = *reinterpret_cast<const f32x4*>(ptab + kpad + prek + 4);
+            const stp3_f32x2 cs[4] = {{s0[0], s0[1]}, {s0[2], s0[3]}, {s1[0], s1[1]}, {s1[2], s1[3]}};
+            const stp3_f32x2 ct[4] = {{t0[0], t0[1]}, {t0[2], t0[3]}, {t1[0], t1[1]}, {t1[2], t1[3]}};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ra[i] = pre_piece<PRE>(ra[i], cs, ct, rmask[i]);
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4*>(buf + lds_piece(rr + 32 * i, j)) = ra[i];
 #pragma unroll
@@ -254,7 +306,6 @@ __global__ __launch_bounds__(256) void conv2d_igemm_kernel(ConvDims d, int tiles
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 
-    const int steps = (d.Ktot + kBK - 1) / kBK;
     load_step();
     store_step(smem);
     __syncthreads();
@@ -999,11 +1050,15 @@ union FragTr {
 };
 
 // BUF: the staging loads through buffer resources (see conv2d_igemm_kernel): both operands smaller than 2 GiB
-template <int TCO, int TCI, bool BUF = false>
+// PRE (kPreAffine / kPreRelu, not with tap folding): X stands for act(scale[ci] * x + shift[ci]) rounded to bf16 (pre_pair), applied
+// to the X pieces between the global load and the LDS store.  A thread's pieces all hold the same 8 channels: its 16 constants
+// live in registers (zero for channels beyond Cin); the contraction runs over the PIXELS, so a piece that stands for padding (a
+// pixel beyond M, a tap outside the image) is masked to zero after the transform.
+template <int TCO, int TCI, bool BUF = false, int PRE = kPreNone>
 __global__ __launch_bounds__(256) void conv2d_wgrad_kernel(ConvDims d, int tiles_ci, int ksteps_per_block, int tap_fold,
                                                            int xcd_chunks, const uint16_t* __restrict__ dy,
                                                            const uint16_t* __restrict__ x,
-                                                           float* __restrict__ partial) {
+                                                           float* __restrict__ partial, const float* __restrict__ pre = nullptr) {
     constexpr int TA = TCO / 64, TB = TCI / 64;            // 32-row MFMA tiles per wave (2 x 2 waves)
     constexpr int kImgA = kBK * TCO * 2;                   // bytes of the dY image; the X image lies behind it
     constexpr int kStage = kBK * (TCO + TCI) * 2;
@@ -1060,6 +1115,17 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_kernel(ConvDims d, int tiles
     const uint32_t cola = (uint32_t)(co0 + pa * 8) * 2u, colb = (uint32_t)chb * 2u;     // BUF: byte offset of the piece in a row
     const uint32_t pitcha = (uint32_t)d.ldy * 2u, pitchb = (uint32_t)d.ldx * 2u;
     const int fold_dh = khb * d.dil_h, fold_dw = kwb * d.dil_w;              // (fold mode) this thread's tap shift
+    stp3_f32x2 pcs[4], pct[4];                                               // PRE: scale / shift of this thread's 8 channels
+    uint32_t bmask[NB];                                                      // PRE: all ones for a loaded piece, zero for padding
+    if (PRE) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                pcs[r][h] = b_ok ? pre[chb + 2 * r + h] : 0.f;
+                pct[r][h] = b_ok ? pre[d.Cin + chb + 2 * r + h] : 0.f;
+            }
+    }
 
     // ---- pixel role: lane l of EVERY wave owns pixel 64 * step + l of the step being loaded.  (n, ho, wo) is set up with
     // one div / mod pair and advanced by 64 = qa * Ho * Wo + qb * Wo + qc pixels per step with two carries
@@ -1092,6 +1158,7 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_kernel(ConvDims d, int tiles
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
                 const int pv = __shfl(pix, rb0 + RB * i);
+                if (PRE) bmask[i] = pv >= 0 ? 0xffffffffu : 0u;
                 if (BUF) rawb[i] = buffer_load16(bbuf, (b_ok & (pv >= 0)) ? (uint32_t)pv * pitchb + colb : kBufOob);
                 else rawb[i] = *reinterpret_cast<const u32x4*>(pv >= 0 ? srcb + (size_t)(unsigned)pv * ldb : zero);
             }
@@ -1114,6 +1181,10 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_kernel(ConvDims d, int tiles
         if (p_ho >= d.Ho) { p_ho -= d.Ho; ++p_n; }
     };
     auto store_step = [&](uint8_t* buf) {
+        if (PRE) {
+#pragma unroll
+            for (int i = 0; i < NB; ++i) rawb[i] = pre_piece<PRE>(rawb[i], pcs, pct, bmask[i]);
+        }
 #pragma unroll
         for (int i = 0; i < NA; ++i) *reinterpret_cast<u32x4*>(buf + wg_piece<TCO>(ra0 + RA * i, pa)) = rawa[i];
 #pragma unroll
@@ -1306,13 +1377,36 @@ inline size_t igemm_lds(int bn, int steps, bool out_f32) {
     return stage > tile ? stage : tile;
 }
 
+template <int TCO, int TCI, int PRE>
+int wgrad_launch_pre(const ConvDims& d, int tco, int tci, int taps, int splits, int ksteps, int xcd, size_t lds, const void* dy,
+                     const void* x, void* workspace, const float* pre, hipStream_t s) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_wgrad_kernel<TCO, TCI, true, PRE>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return -(int)e;
+    hipLaunchKernelGGL((conv2d_wgrad_kernel<TCO, TCI, true, PRE>), dim3(tco * tci, taps, splits), dim3(256), lds, s, d, tci,
+                       ksteps, 0, xcd, (const uint16_t*)dy, (const uint16_t*)x, (float*)workspace, pre);
+    return STP3_OK;
+}
+
+// pre / pre_act: the operand-side BatchNorm of the kernel's PRE mode (buffer-addressed staging only, no tap folding), or null
 template <int TCO, int TCI>
 int wgrad_launch(const ConvDims& d, int tco, int tci, int taps, int splits, int ksteps, int fold, const void* dy,
-                 const void* x, void* workspace, hipStream_t s) {
+                 const void* x, void* workspace, hipStream_t s, const float* pre = nullptr, int pre_act = STP3_ACT_NONE) {
     const size_t lds = (size_t)2 * (TCO + TCI) * kBK * 2;
     // XCD-contiguous workgroup order when the grid is a 32-bit count and the layer has at most a 3x3's worth of taps
     const int xcd = taps <= 9 && (int64_t)tco * tci * taps * splits < (1LL << 31);
     const bool buf = (size_t)d.M * d.ldy * 2 < (1ull << 31) && (size_t)d.N * d.H * d.W * d.ldx * 2 < (1ull << 31);
+    if (pre) {
+        if (!buf || fold) return STP3_EUNSUP;
+        // The 64 x 64 tile keeps 5 workgroups per CU in 96 registers and ALL of the CU's LDS: no room for 16 constants.  Its
+        // layers (at most 64 channels on either side: small) run the 64 x 128 instantiation on the same plan -- same grid, same
+        // pixel splits, the upper 64 columns of the tile beyond Cin and never loaded: the same sums in the same order.
+        constexpr int TCIP = (TCO == 64 && TCI == 64) ? 128 : TCI;
+        const size_t ldsp = (size_t)2 * (TCO + TCIP) * kBK * 2;
+        if (pre_act == STP3_ACT_RELU)
+            return wgrad_launch_pre<TCO, TCIP, kPreRelu>(d, tco, tci, taps, splits, ksteps, xcd, ldsp, dy, x, workspace, pre, s);
+        return wgrad_launch_pre<TCO, TCIP, kPreAffine>(d, tco, tci, taps, splits, ksteps, xcd, ldsp, dy, x, workspace, pre, s);
+    }
     if (buf) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_wgrad_kernel<TCO, TCI, true>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1365,6 +1459,18 @@ int igemm_launch_one(const ConvDims& d, dim3 grid, size_t lds, int tiles_co, con
     if (e != hipSuccess) return -(int)e;
     hipLaunchKernelGGL((conv2d_igemm_kernel<BN, MODE, ACT>), grid, dim3(256), lds, s, d, tiles_co, (const uint16_t*)x,
                        (const uint16_t*)w, bias, y, partial, ep);
+    return STP3_OK;
+}
+
+// the PRE instantiations: plain mode, buffer-addressed staging
+template <int BN, int PRE>
+int igemm_launch_pre(const ConvDims& d, dim3 grid, size_t lds, int tiles_co, const void* x, const void* w, const float* bias, void* y,
+                     const EpiArgs& ep, hipStream_t s) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_igemm_kernel<BN, kModePlain, STP3_ACT_NONE, true, PRE>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return -(int)e;
+    hipLaunchKernelGGL((conv2d_igemm_kernel<BN, kModePlain, STP3_ACT_NONE, true, PRE>), grid, dim3(256), lds, s, d, tiles_co,
+                       (const uint16_t*)x, (const uint16_t*)w, bias, y, (float*)nullptr, ep);
     return STP3_OK;
 }
 
@@ -1538,7 +1644,14 @@ int igemm_run(const stp3_conv_dims* p, const void* x, const void* w, const float
         ep.act = act;
         return pointwise_run(d, x, w, y, sums, partial, gx, s, mode, ep);
     }
-    if (ep.add) {
+    if (ep.pre) {
+        // operand-side BatchNorm (stp3_conv2d_fwd_pre): 1x1 / stride 1 / unpadded, plain mode, always the tiled kernel with
+        // buffer-addressed staging; the constants' LDS table (at most 32 KB: 4096 input channels) lies behind everything else
+        if (mode != kModePlain || sums || ep.add || p->KH != 1 || p->KW != 1 || p->stride != 1 || p->pad_h || p->pad_w ||
+            p->H != p->Ho || p->W != p->Wo || p->Cin > 4096)
+            return STP3_EUNSUP;
+        if (!((size_t)d.N * d.H * d.W * d.ldx * 2 < (1ull << 31) && (size_t)d.Cout * d.Ktot * 2 < (1ull << 31))) return STP3_EUNSUP;
+    } else if (ep.add) {
         // the skip-gradient addend: plain mode, bf16 output, whole 16-byte channel pieces on both sides
         if (mode != kModePlain || d.out_f32 || p->Cout % 8 || p->ldy % 8 || ep.ldadd % 8 || ep.ldadd < p->Cout ||
             ((uintptr_t)ep.add & 15) || ((uintptr_t)y & 15))
@@ -1566,6 +1679,17 @@ int igemm_run(const stp3_conv_dims* p, const void* x, const void* w, const float
     if ((int64_t)gx * tiles_co >= (1LL << 31)) return STP3_EUNSUP;
     const dim3 grid(gx * (unsigned)tiles_co);                // 1-D: the kernel derives (pixel tile, channel tile) itself
     int rc;
+    if (ep.pre) {
+        ep.pre_off = (int)((lds + 15) / 16 * 16);
+        lds = (size_t)ep.pre_off + (size_t)2 * steps * kBK * sizeof(float);
+        if (act == STP3_ACT_RELU)
+            rc = wide ? igemm_launch_pre<128, kPreRelu>(d, grid, lds, tiles_co, x, w, bias, y, ep, s)
+                      : igemm_launch_pre<64, kPreRelu>(d, grid, lds, tiles_co, x, w, bias, y, ep, s);
+        else
+            rc = wide ? igemm_launch_pre<128, kPreAffine>(d, grid, lds, tiles_co, x, w, bias, y, ep, s)
+                      : igemm_launch_pre<64, kPreAffine>(d, grid, lds, tiles_co, x, w, bias, y, ep, s);
+        return rc ? rc : status();
+    }
 #define STP3_IGEMM_MODE(MODE)                                                                                                \
     rc = wide ? igemm_launch_act<128, MODE>(act, d, grid, lds, tiles_co, x, w, bias, y, partial, ep, s)                       \
               : igemm_launch_act<64, MODE>(act, d, grid, lds, tiles_co, x, w, bias, y, partial, ep, s)
@@ -1590,6 +1714,15 @@ extern "C" {
 int stp3_conv2d_fwd(const stp3_conv_dims* p, const void* x, const void* w, const float* bias, void* y, float* sums,
                     void* workspace, size_t workspace_bytes, void* stream) {
     return igemm_run(p, x, w, bias, y, sums, workspace, workspace_bytes, stream, kModePlain, STP3_ACT_NONE, EpiArgs());
+}
+
+// ---- a 1x1 convolution of bf16(act(scale[ci] * x + shift[ci])): the BatchNorm apply pass in the operand load (PRE) ------
+int stp3_conv2d_fwd_pre(const stp3_conv_dims* p, const void* x, const void* w, const float* bias, const float* pre_coef,
+                        int32_t pre_act, void* y, void* stream) {
+    if (!pre_coef || (pre_act != STP3_ACT_NONE && pre_act != STP3_ACT_RELU)) return STP3_EINVAL;
+    EpiArgs ep = EpiArgs();
+    ep.pre = pre_coef;
+    return igemm_run(p, x, w, bias, y, nullptr, nullptr, 0, stream, kModePlain, pre_act, ep);
 }
 
 int stp3_conv2d_fwd_add(const stp3_conv_dims* p, const void* x, const void* w, const float* bias, const void* add, int32_t ldadd,
@@ -1701,9 +1834,14 @@ int stp3_conv2d_wgrad_workspace(const stp3_conv_dims* p, size_t* bytes) {
 }
 
 // the main kernel of the weight gradient: partial[split][Cout][KH][KW][Cin] into `workspace`; *splits_out = the splits
+// pre_coef / pre_act: X stands for bf16(act(scale[ci] * x + shift[ci])) (the kernel's PRE mode: 1x1, stride-1, unpadded layers)
 static int wgrad_partials(const stp3_conv_dims* p, const void* dy, const void* x, void* workspace, size_t workspace_bytes,
-                          int* splits_out, hipStream_t s) {
+                          int* splits_out, hipStream_t s, const float* pre_coef = nullptr, int pre_act = STP3_ACT_NONE) {
     if (!p || !dy || !x || !workspace) return STP3_EINVAL;
+    if (pre_coef) {
+        if (pre_act != STP3_ACT_NONE && pre_act != STP3_ACT_RELU) return STP3_EINVAL;
+        if (p->KH != 1 || p->KW != 1 || p->stride != 1 || p->pad_h || p->pad_w || p->H != p->Ho || p->W != p->Wo) return STP3_EUNSUP;
+    }
     if (p->N <= 0 || p->H <= 0 || p->W <= 0 || p->Cin <= 0 || p->Cout <= 0 || p->Ho <= 0 || p->Wo <= 0 || p->KH <= 0 ||
         p->KW <= 0 || p->stride <= 0 || p->dil_h <= 0 || p->dil_w <= 0 || p->pad_h < 0 || p->pad_w < 0)
         return STP3_EINVAL;
@@ -1727,10 +1865,11 @@ static int wgrad_partials(const stp3_conv_dims* p, const void* dy, const void* x
     d.dil_h = p->dil_h; d.dil_w = p->dil_w; d.ldx = p->ldx; d.ldy = p->ldy;
     d.out_f32 = 1; d.has_bias = 0; d.M = (int)M; d.kchunks = 0; d.Ktot = p->KH * p->KW * p->Cin;
     int rc;
-    if (tco_sz == 128 && tci_sz == 128) rc = wgrad_launch<128, 128>(d, tco, tci, taps, splits, ksteps, fold, dy, x, workspace, s);
-    else if (tco_sz == 128) rc = wgrad_launch<128, 64>(d, tco, tci, taps, splits, ksteps, fold, dy, x, workspace, s);
-    else if (tci_sz == 128) rc = wgrad_launch<64, 128>(d, tco, tci, taps, splits, ksteps, fold, dy, x, workspace, s);
-    else rc = wgrad_launch<64, 64>(d, tco, tci, taps, splits, ksteps, fold, dy, x, workspace, s);
+    if (tco_sz == 128 && tci_sz == 128)
+        rc = wgrad_launch<128, 128>(d, tco, tci, taps, splits, ksteps, fold, dy, x, workspace, s, pre_coef, pre_act);
+    else if (tco_sz == 128) rc = wgrad_launch<128, 64>(d, tco, tci, taps, splits, ksteps, fold, dy, x, workspace, s, pre_coef, pre_act);
+    else if (tci_sz == 128) rc = wgrad_launch<64, 128>(d, tco, tci, taps, splits, ksteps, fold, dy, x, workspace, s, pre_coef, pre_act);
+    else rc = wgrad_launch<64, 64>(d, tco, tci, taps, splits, ksteps, fold, dy, x, workspace, s, pre_coef, pre_act);
     if (rc) return rc;
     *splits_out = splits;
     return status();
@@ -1749,11 +1888,24 @@ int stp3_conv2d_wgrad(const stp3_conv_dims* p, const void* dy, const void* x, fl
     return status();
 }
 
-int stp3_conv2d_wgrad_partials(const stp3_conv_dims* p, const void* dy, const void* x, void* partials, size_t partials_bytes,
-                               int32_t* splits, void* stream) {
+int stp3_conv2d_wgrad_pre(const stp3_conv_dims* p, const void* dy, const void* x, const float* pre_coef, int32_t pre_act, float* dw,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    if (!dw || !pre_coef) return STP3_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    int splits = 0;
+    int rc = wgrad_partials(p, dy, x, workspace, workspace_bytes, &splits, s, pre_coef, pre_act);
+    if (rc) return rc;
+    const size_t wsize = (size_t)p->Cout * p->KH * p->KW * p->Cin;
+    hipLaunchKernelGGL(conv2d_wgrad_reduce_kernel, dim3((unsigned)((wsize + 63) / 64)), dim3(256), 0, s, splits, wsize,
+                       (const float*)workspace, dw);
+    return status();
+}
+
+int stp3_conv2d_wgrad_partials(const stp3_conv_dims* p, const void* dy, const void* x, const float* pre_coef, int32_t pre_act,
+                               void* partials, size_t partials_bytes, int32_t* splits, void* stream) {
     if (!splits) return STP3_EINVAL;
     int n = 0;
-    int rc = wgrad_partials(p, dy, x, partials, partials_bytes, &n, (hipStream_t)stream);
+    int rc = wgrad_partials(p, dy, x, partials, partials_bytes, &n, (hipStream_t)stream, pre_coef, pre_act);
     if (rc) return rc;
     *splits = n;
     return STP3_OK;

@@ -268,8 +268,11 @@ SIGNATURES = {
                                             ctypes.c_double, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
     'stp3_conv2d_wgrad_workspace': (c_int, [ctypes.POINTER(ConvDims), ctypes.POINTER(c_size_t)]),
     'stp3_conv2d_wgrad': (c_int, [ctypes.POINTER(ConvDims), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'stp3_conv2d_wgrad_partials': (c_int, [ctypes.POINTER(ConvDims), c_void_p, c_void_p, c_void_p, c_size_t,
+    'stp3_conv2d_wgrad_partials': (c_int, [ctypes.POINTER(ConvDims), c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_size_t,
                                            ctypes.POINTER(c_int32), c_void_p]),
+    'stp3_conv2d_fwd_pre': (c_int, [ctypes.POINTER(ConvDims), c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    'stp3_conv2d_wgrad_pre': (c_int, [ctypes.POINTER(ConvDims), c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
     'stp3_conv2d_wgrad_reduce_batch': (c_int, [c_int32, ctypes.POINTER(WgradJob), c_void_p]),
     'stp3_conv2d_prep_weights': (c_int, [c_void_p, c_int32, ctypes.c_int64, c_void_p]),
     'stp3_conv2d_scatter_weight_grads': (c_int, [c_void_p, c_int32, ctypes.c_int64, c_void_p]),

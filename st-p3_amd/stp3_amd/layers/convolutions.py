@@ -184,13 +184,10 @@ class ASPP(nn.Module):
         self.project = nn.Sequential(nn.Conv2d(len(self.convs) * out_channels, out_channels, 1, bias=False),
                                      nn.BatchNorm2d(out_channels), nn.ReLU(), nn.Dropout(0.5))
 
-    def _branches_into_one_buffer(self, xs):
-        """The spatial branches (1x1 and the dilated 3x3s, each conv -> BN -> ReLU) with their results written straight into
-        the channel slices of ONE buffer -- the concatenation the projection reads -- instead of four tensors and a
-        ``torch.cat`` (491 MB written and read again for the temporal head of configs[2]).  None when a branch does not
-        qualify for the fused operator (dropped taps, evaluation mode, float32): then the plain route is taken."""
-        from .fused import _fusable_conv_bn, _sync_world as sync_world
-        from .. import ops_fused
+    def _one_buffer_branches(self, xs):
+        """[(conv, bn)] of the spatial branches when they qualify for the one-buffer route of ``_branches_into_one_buffer``, else
+        None (dropped taps, evaluation mode, float32)."""
+        from .fused import _fusable_conv_bn
         convs = [(m[0], m[1]) for m in self.convs[:-1]]
         h, w = xs[0].shape[-2:]
         if not all(_fusable_conv_bn(c, bn, xs[0]) for c, bn in convs):
@@ -202,6 +199,35 @@ class ASPP(nn.Module):
             return None
         if xs[0].dtype != torch.bfloat16:
             return None
+        return convs
+
+    def _foldable_branches(self, xs):
+        """[(conv, bn)] of the spatial branches when their BatchNorm + ReLU can be applied in the projection's operand load
+        (``fused.pre_fold_ok``: the one-buffer route's conditions, single process, outside the inference engine's scope), else None."""
+        from . import fused
+        convs = self._one_buffer_branches(xs)
+        proj = self.project[0]
+        if convs is None or fused.eval_coef(self.project[1]) is not None:
+            return None
+        n_sp = sum(c.out_channels for c, _ in convs)
+        w_sp = proj.weight[:, :n_sp]
+        if not all(fused.pre_fold_ok(c, b, xs[0], w_sp) for c, b in convs):
+            return None
+        n, _, h, w = xs[0].shape
+        from .. import ops_fused
+        return convs if n * h * w * n_sp * 2 < (1 << 31) and ops_fused.pre_fold_pays(n, h, w, n_sp) else None
+
+    def _branches_into_one_buffer(self, xs):
+        """The spatial branches (1x1 and the dilated 3x3s, each conv -> BN -> ReLU) with their results written straight into
+        the channel slices of ONE buffer -- the concatenation the projection reads -- instead of four tensors and a
+        ``torch.cat`` (491 MB written and read again for the temporal head of configs[2]).  None when a branch does not
+        qualify for the fused operator (dropped taps, evaluation mode, float32): then the plain route is taken."""
+        from .. import ops_fused
+        convs = self._one_buffer_branches(xs)
+        if convs is None:
+            return None
+        h, w = xs[0].shape[-2:]
+        co = convs[0][0].out_channels
         n = xs[0].shape[0]
         buf = torch.empty((n, co * len(convs), h, w), dtype=torch.bfloat16, device=xs[0].device, memory_format=torch.channels_last)
         parts = []
@@ -213,7 +239,7 @@ class ASPP(nn.Module):
     def forward(self, x):
         # the branches read one tensor: their input gradients are added in one pass (ops.fan_out), not pairwise
         xs = ops.fan_out(x, len(self.convs)) if x.is_cuda else [x] * len(self.convs)
-        spatial = None
+        spatial = folded = None
         if _sync_world(self.convs[0][1]) > 1:
             # N > 1 ranks: the five branches are siblings -- their BatchNorm statistics travel in ONE exchange per pass
             members = [conv_bn_act_member(xs[0], self.convs[0][0], self.convs[0][1], ACT_RELU)]
@@ -221,16 +247,22 @@ class ASPP(nn.Module):
             members.append(dict(bn=self.convs[-1][2], x=self.convs[-1].conv_only(xs[-1]), act=ACT_RELU))
             *branches, pooled = bn_act_group(members)
         else:
-            spatial = self._branches_into_one_buffer(xs)
-            if spatial is None:
-                branches = [run_fused(self.convs[0], xs[0])] + [conv(xi) for conv, xi in zip(self.convs[1:-1], xs[1:-1])]
+            folded = self._foldable_branches(xs)
+            if folded is None:
+                spatial = self._branches_into_one_buffer(xs)
+                if spatial is None:
+                    branches = [run_fused(self.convs[0], xs[0])] + [conv(xi) for conv, xi in zip(self.convs[1:-1], xs[1:-1])]
             pooled = self.convs[-1](xs[-1])                          # (N, C, 1, 1)
-        if spatial is None:
-            spatial = torch.cat(branches, dim=1)
         proj, bn, act, drop = self.project
-        n_sp = spatial.shape[1]
+        if folded is not None:
+            n_sp = sum(c.out_channels for c, _ in folded)         # (the concatenation is never formed; bf16 like xs[0])
+        else:
+            if spatial is None:
+                spatial = torch.cat(branches, dim=1)
+            n_sp = spatial.shape[1]
         # (split, not two slices: one concatenation in backward instead of two zero-fills, two copies and an addition)
-        if n_sp % 8 == 0 and proj.weight.shape[0] % 8 == 0 and ops.assembled_weight_supported(spatial, (proj.weight,)):
+        if n_sp % 8 == 0 and proj.weight.shape[0] % 8 == 0 and \
+                ops.assembled_weight_supported(xs[0] if folded is not None else spatial, (proj.weight,)):
             # the columns of the spatial branches as a weight of their own (ops.assembled_weight); the pooled branch's columns
             # go another way (below) and write their part of the parameter's gradient themselves (ops.weight_columns)
             w_sp = ops.assembled_weight((id(proj), 'spatial'), (proj.weight.shape[0], n_sp, 1, 1),
@@ -244,7 +276,14 @@ class ASPP(nn.Module):
             sbias = pooled_bias(hp(conv1x1_on_vector(pooled, w_pool).flatten(1)))
             y = fused.eval_conv2d_bn_act(spatial, w_sp, None, 1, 0, 1, bn, ACT_RELU, sbias=sbias)
             return drop(y if y is not None else bn_act(bn, conv2d(spatial, w_sp), ACT_RELU, sbias=sbias))
-        y = conv2d(spatial, w_sp)
+        if folded is not None:
+            # the branches' BatchNorm + ReLU in the projection's operand load: their convolution outputs side by side in one
+            # buffer, their constants in one table, the normalised concatenation never stored
+            from .. import ops_fused
+            y = ops_fused.conv_bn_act_conv1x1([(xi, c.weight, c.bias, b, c.stride, c.padding, c.dilation)
+                                               for (c, b), xi in zip(folded, xs)], ACT_RELU, w_sp, None)
+        else:
+            y = conv2d(spatial, w_sp)
         # the pooled branch is a constant plane per sample: its projection is a per-sample bias, folded
         # into the fused BatchNorm instead of a broadcast add over the whole map
         sbias = pooled_bias(hp(conv1x1_on_vector(pooled, w_pool).flatten(1)))

@@ -514,12 +514,45 @@ def conv_bn_act_layer(x, conv, bn, act, res=None, res_mode=RES_NONE):
     return bn_act(bn, conv_module(conv, x), act, res=res, res_mode=res_mode)
 
 
+def pre_fold_ok(conv, bn, x, w2):
+    """conv -> bn -> ReLU -> 1x1 convolution with weight ``w2``, the normalised tensor read by nothing else: may the BatchNorm
+    apply pass move into the 1x1 layer's operand load (``ops_fused.conv_bn_act_conv1x1``)?  Training mode on the bf16 kernels in
+    one process; evaluation, the inference engine's scope, float32 / EMULATE_BF16, shared statistics (``_sync_world``, which
+    includes ops.FORCE_EXCHANGE), odd channel counts and CPU tensors keep the separate operators."""
+    from .. import ops_fused
+    return (ops_fused.PRE_FOLD and not EMULATE_BF16 and _EVAL_COEFS is None and _fusable_conv_bn(conv, bn, x)
+            and _sync_world(bn) <= 1 and ops_fused.pre_fold_supported(x, conv.weight, conv.stride, conv.padding, conv.dilation, w2))
+
+
+def _conv_output_pays(conv, x):
+    """``ops_fused.pre_fold_pays`` for the output of ``conv`` on ``x``."""
+    from .. import ops_fused
+    s, p, d = ops._pair(conv.stride), ops._pair(conv.padding), ops._pair(conv.dilation)
+    ho = ops._conv_out(x.shape[2], conv.kernel_size[0], s[0], p[0], d[0])
+    wo = ops._conv_out(x.shape[3], conv.kernel_size[1], s[1], p[1], d[1])
+    return ops_fused.pre_fold_pays(x.shape[0], ho, wo, conv.out_channels)
+
+
+def _plain_1x1(m):
+    return (type(m) is nn.Conv2d and m.kernel_size == (1, 1) and m.stride == (1, 1) and m.padding == (0, 0) and m.groups == 1
+            and m.padding_mode == 'zeros')
+
+
 def run_fused(seq, x):
     """Run an ``nn.Sequential`` with every ``BatchNorm -> ReLU`` pair (or lone BatchNorm) fused."""
     mods = list(seq)
     i = 0
     while i < len(mods):
         m = mods[i]
+        if (i + 3 < len(mods) and isinstance(mods[i + 2], nn.ReLU) and _plain_1x1(mods[i + 3])
+                and pre_fold_ok(m, mods[i + 1], x, mods[i + 3].weight) and _conv_output_pays(m, x)):
+            # Conv2d -> BatchNorm -> ReLU -> Conv2d(1x1): the tail of a DeepLabHead, a decoder head
+            from .. import ops_fused
+            last = mods[i + 3]
+            x = ops_fused.conv_bn_act_conv1x1([(x, m.weight, m.bias, mods[i + 1], m.stride, m.padding, m.dilation)], ACT_RELU,
+                                              last.weight, last.bias)
+            i += 4
+            continue
         if i + 1 < len(mods) and _fusable_conv_bn(m, mods[i + 1], x):
             from .. import ops_fused
             relu = i + 2 < len(mods) and isinstance(mods[i + 2], nn.ReLU)

@@ -6,7 +6,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..layers.convolutions import UpsamplingAdd
-from ..layers.fused import ACT_RELU, _sync_world, bn_act, bn_act_group, conv_bn_act_layer, conv_bn_act_member, conv_module, run_fused
+from ..layers.fused import ACT_RELU, _sync_world, bn_act, bn_act_group, conv_bn_act_layer, conv_bn_act_member, conv_module, pre_fold_ok, run_fused
 from .resnet import resnet18
 
 
@@ -44,6 +44,17 @@ class _SelectFrame(torch.autograd.Function):
 # convolution per output channel), the operand is staged once instead of once per head, five data gradients and their
 # additions become one.  Training mode on the bf16 kernels; everything else takes the heads one by one.
 MERGE_HEADS = True
+
+
+class _MergedBn:
+    """The BatchNorms of the merged heads seen as ONE module by ``ops_fused.conv_bn_act_conv1x1``: parameters side by side, the
+    packed running statistics, the first head's momentum / eps (all heads agree: checked by the caller); the batch counters are
+    the heads' own and were bumped by the caller."""
+    num_batches_tracked = None
+
+    def __init__(self, bns, gamma, beta, running_mean, running_var):
+        self.weight, self.bias, self.running_mean, self.running_var = gamma, beta, running_mean, running_var
+        self.momentum, self.eps, self.training, self.track_running_stats = bns[0].momentum, bns[0].eps, True, True
 
 
 class Decoder(nn.Module):
@@ -121,7 +132,15 @@ class Decoder(nn.Module):
                 ops.bn_momentum(bns[0]), float(bns[0].eps), int(ACT_RELU),
                 int(ops.RES_NONE), 1, (1, 1), (1, 1), None if shared else False, None)
         out = {}
-        if shared and others:
+        # (single process: the merged BatchNorm + ReLU is applied in the operand load of the block-diagonal 1x1 layer below)
+        fold = not shared and all(m.bias is not None for m in lasts) and \
+            pre_fold_ok(convs[0], bns[0], x, lasts[0].weight) and x.shape[0] * x.shape[2] * x.shape[3] * len(lasts) * c * 2 < (1 << 31) and \
+            ops_fused.pre_fold_pays(x.shape[0], x.shape[2], x.shape[3], len(lasts) * c)
+        if fold:
+            mid = None
+            for name, head, inp in others:
+                out[name] = run_fused(head, inp)
+        elif shared and others:
             mids = bn_act_group([('conv_bn_act', args, bns[0])]
                                 + [conv_bn_act_member(inp, head[0], head[1], ACT_RELU) for _, head, inp in others])
             mid = mids[0]
@@ -142,11 +161,16 @@ class Decoder(nn.Module):
                 co += m.out_channels
             w2 = ops.assembled_weight((id(self), 'heads 1x1'), (lanes_out, len(lasts) * c, 1, 1), pieces)
             b2 = torch.cat([m.bias for m in lasts] + ([m.bias.new_zeros(lanes_out - n_out)] if lanes_out != n_out else []))
-            y = conv2d(mid, w2, b2)[:, :n_out]
         else:
             w2 = torch.block_diag(*[m.weight.flatten(1) for m in lasts])[:, :, None, None]    # (sum of outputs, heads * C, 1, 1)
             b2 = torch.cat([m.bias for m in lasts])
+        if fold:
+            y = ops_fused.conv_bn_act_conv1x1([(x, w1, None, _MergedBn(bns, gamma, beta, running_mean, running_var), 1, (1, 1), (1, 1))],
+                                              ACT_RELU, w2, b2)
+        else:
             y = conv2d(mid, w2, b2)
+        if assembled:
+            y = y[:, :n_out]
         # (one split: its backward writes the heads' gradients into ONE tensor, instead of a zero-fill, a copy and an addition per head)
         for (name, head), t in zip(heads, y.split([m.out_channels for m in lasts], dim=1)):
             for extra in list(head)[4:]:                                 # the sigmoid of the centerness head

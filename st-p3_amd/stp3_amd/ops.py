@@ -13,6 +13,7 @@ PyTorch is used for device memory, streams and autograd plumbing only.
 """
 import ctypes
 import os
+import types
 import weakref
 
 import torch
@@ -1267,11 +1268,12 @@ class SkipCarrier:
         return g
 
 
-def _conv2d_launch(x, wb, bias, stride, pad, dil, out_dtype, sums_ptr=None, out_hw=None, add=None):
+def _conv2d_launch(x, wb, bias, stride, pad, dil, out_dtype, sums_ptr=None, out_hw=None, add=None, out_slot=None):
     """x (N,Cin,H,W) bf16 with channels-last memory (row stride ld >= Cin); wb (Cout,Cin,KH,KW) bf16 channels-last.
     ``sums_ptr``: device address of a float32 [2][Cout] buffer that receives the BatchNorm statistics of y (bf16 y).
     ``out_hw``: output size when it is not the one ``pad`` implies on both sides (``pad`` is the top / left padding;
-    taps that fall off the bottom / right edge read zeros like any other padding)."""
+    taps that fall off the bottom / right edge read zeros like any other padding).
+    ``out_slot`` = (buffer, first channel): y is that channel slice of a wider channels-last tensor (``slot_view``)."""
     n, cin, h, w = x.shape
     cout, _, kh, kw = wb.shape
     x, ldx = _rows_view(x)
@@ -1279,8 +1281,13 @@ def _conv2d_launch(x, wb, bias, stride, pad, dil, out_dtype, sums_ptr=None, out_
         ho, wo = _conv_out(h, kh, stride, pad[0], dil[0]), _conv_out(w, kw, stride, pad[1], dil[1])
     else:
         ho, wo = out_hw
-    y = torch.empty((n, cout, ho, wo), dtype=out_dtype, device=x.device, memory_format=torch.channels_last)
-    dims = _lib.ConvDims(n, h, w, cin, ho, wo, cout, kh, kw, stride, pad[0], pad[1], dil[0], dil[1], ldx, cout,
+    ldy = cout
+    if out_slot is None:
+        y = torch.empty((n, cout, ho, wo), dtype=out_dtype, device=x.device, memory_format=torch.channels_last)
+    else:
+        assert add is None
+        y, ldy = slot_view(out_slot, types.SimpleNamespace(shape=(n, cout, ho, wo), dtype=out_dtype))
+    dims = _lib.ConvDims(n, h, w, cin, ho, wo, cout, kh, kw, stride, pad[0], pad[1], dil[0], dil[1], ldx, ldy,
                          _lib.DTYPE_F32 if out_dtype == torch.float32 else _lib.DTYPE_BF16, int(bias is not None))
     lib = _lib.lib()
     ws_ptr, ws_bytes = None, 0
@@ -1318,12 +1325,15 @@ _CONV_WORKSPACE = {}
 DIRECT_BUCKET_GRADS = True
 
 
-def _conv2d_wgrad(dy, x, wshape, stride, pad, dil, leaf=None):
+def _conv2d_wgrad(dy, x, wshape, stride, pad, dil, leaf=None, pre=None):
     """dw (Cout,Cin,KH,KW) float32, channels-last memory, through stp3_conv2d_wgrad (bf16 operands).
     ``leaf``: the tensor the operator received as its weight.  When that is a LEAF parameter without a gradient yet, in
     float32 and in the memory order of dw, autograd's AccumulateGrad keeps the tensor handed back as the parameter's ``.grad``
-    without launching anything -- so it can be written where the optimizer reads it (below)."""
+    without launching anything -- so it can be written where the optimizer reads it (below).
+    ``pre`` = (float32 [scale | shift][Cin], activation): x is the OUTPUT OF THE CONVOLUTION in front of a BatchNorm whose apply pass
+    was folded into this 1x1 layer's operand load (stp3_conv2d_wgrad_pre); every route below takes it."""
     cout, cin, kh, kw = wshape
+    pre_ptr, pre_act = (None, 0) if pre is None else (pre[0].data_ptr(), int(pre[1]))
     n, _, h, w = x.shape
     x, ldx = _rows_view(x)
     dy, ldy = _rows_view(dy)
@@ -1369,14 +1379,19 @@ def _conv2d_wgrad(dy, x, wshape, stride, pad, dil, leaf=None):
         slot = arena.take(nbytes.value)
         if slot is not None:
             splits = ctypes.c_int32()
-            check(lib.stp3_conv2d_wgrad_partials(ctypes.byref(dims), _ptr(dy), _ptr(x), slot, ctypes.c_size_t(nbytes.value),
-                                                 ctypes.byref(splits), _stream()), 'stp3_conv2d_wgrad_partials')
+            check(lib.stp3_conv2d_wgrad_partials(ctypes.byref(dims), _ptr(dy), _ptr(x), pre_ptr, pre_act, slot,
+                                                 ctypes.c_size_t(nbytes.value), ctypes.byref(splits), _stream()),
+                  'stp3_conv2d_wgrad_partials')
             arena.jobs.append((slot, dw.data_ptr(), cout * cin * kh * kw, splits.value))
             return dw
     ws = _CONV_WORKSPACE.get(key)
     if ws is None or ws.numel() < nbytes.value:
         ws = torch.empty(max(nbytes.value, 64 << 20), dtype=torch.uint8, device=x.device)
         _CONV_WORKSPACE[key] = ws
+    if pre is not None:
+        check(lib.stp3_conv2d_wgrad_pre(ctypes.byref(dims), _ptr(dy), _ptr(x), pre_ptr, pre_act, _ptr(dw), _ptr(ws),
+                                        ctypes.c_size_t(nbytes.value), _stream()), 'stp3_conv2d_wgrad_pre')
+        return dw
     check(lib.stp3_conv2d_wgrad(ctypes.byref(dims), _ptr(dy), _ptr(x), _ptr(dw), _ptr(ws), ctypes.c_size_t(nbytes.value),
                                 _stream()), 'stp3_conv2d_wgrad')
     return dw

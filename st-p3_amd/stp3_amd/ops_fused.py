@@ -343,6 +343,183 @@ def pointwise_bn_act(x, conv, bn, act, group=None, skip_carrier=None):
                                  float(bn.eps), int(act), group, skip_carrier)
 
 
+# conv -> BatchNorm -> ReLU -> 1x1 conv chains whose normalised tensor has no other reader run as ``_ConvBnActConv1x1``: the
+# BatchNorm apply pass happens in the operand load of the 1x1 convolution.  Off: the separate operators (same bits).
+PRE_FOLD = True
+# ... where it pays: the fold trades one write + one read of the normalised tensor against vector instructions in the consumers'
+# staging and one stp3_bn_finalize launch per producer.  Measured (profiles/prefold_ab.txt): 47-211 us per layer gained on the
+# 61-246 M-element tensors of the 200 x 200 x 12 BEV heads, 3-5 us -- nothing -- on the 10 M-element ones (hd-map head on 4 frames,
+# the encoder heads' tails at 28 x 60), whose apply pass is 8-13 us.  Below this many elements the separate operators stay.
+PRE_FOLD_MIN_ELEMENTS = 1 << 24
+_N_PRODUCER_ARGS = 12
+
+
+class _ConvBnActConv1x1(torch.autograd.Function):
+    """y = conv1x1(act(BN_k(conv_k(x_k))) side by side over k, w2) + b2 -- one or several conv -> BatchNorm -> activation
+    producers (the ASPP branches; a 3x3 layer in front of a head's output convolution) feeding ONE 1x1 convolution, WITHOUT the
+    normalised tensor in memory (stp3/layers/convolutions.py:183-280, stp3/models/decoder.py:42-66).
+
+      forward   per producer: stp3_conv2d_fwd writes z_k into its channel slice of one buffer (statistics from its epilogue) and
+                stp3_bn_finalize turns them into (scale, shift) + the running statistics; stp3_conv2d_fwd_pre contracts
+                bf16(act(scale * z + shift)) -- bit for bit what stp3_bn_apply_fwd would have stored -- with w2
+      backward  data gradient of the 1x1 layer as ever; its weight gradient through stp3_conv2d_wgrad_pre (same operand, from z);
+                then per producer what ``_ConvBnAct.backward_steps`` runs: stp3_bn_bwd_reduce / stp3_bn_apply_bwd on (d act, z)
+                -- they never needed the normalised tensor -- and the producer's convolution backward
+
+    One write and one read of the normalised tensor less than the separate operators, the same values everywhere.  Single
+    process, training mode, bf16, channel counts in whole 16-byte pieces (``pre_fold_supported``).
+    Arguments: act, w2, b2, number of producers, then per producer (x, weight, conv bias, gamma, beta, running_mean, running_var,
+    momentum, eps, stride, padding, dilation)."""
+
+    @staticmethod
+    def forward(ctx, act, w2, b2, n_prod, *flat):
+        lib = _lib.lib()
+        stream = ops._stream_handle()
+        prods = [flat[k * _N_PRODUCER_ARGS:(k + 1) * _N_PRODUCER_ARGS] for k in range(n_prod)]
+        xs, wbs, params, cfgs = [], [], [], []
+        for x, weight, cbias, gamma, beta, rmean, rvar, momentum, eps, stride, pad, dil in prods:
+            ops._need_gpu(x, weight)
+            xs.append(x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16))
+            wbs.append(ops._bf16_weights(weight)[0])
+        couts = [wb.shape[0] for wb in wbs]
+        ctot = sum(couts)
+        n, _, h, w = xs[0].shape
+        (_, _, _, _, _, _, _, _, _, stride, pad, dil), (kh, kw) = prods[0], wbs[0].shape[2:]
+        ho, wo = ops._conv_out(h, kh, stride, pad[0], dil[0]), ops._conv_out(w, kw, stride, pad[1], dil[1])
+        dev = xs[0].device
+        zbuf = torch.empty((n, ctot, ho, wo), dtype=torch.bfloat16, device=dev, memory_format=torch.channels_last)
+        count = float(n * ho * wo)
+        stats, c0 = [], 0
+        for x, wb, c, (_, weight, cbias, gamma, beta, rmean, rvar, momentum, eps, stride, pad, dil) in zip(xs, wbs, couts, prods):
+            stat = torch.empty(6 * c, dtype=torch.float32, device=dev)      # sum | sum of squares | scale | shift | mean | invstd
+            z = ops._conv2d_launch(x, wb, ops._f32(cbias), stride, pad, dil, torch.bfloat16, sums_ptr=stat.data_ptr(),
+                                   out_slot=(zbuf, c0))
+            if tuple(z.shape[2:]) != (ho, wo):
+                raise _lib.Stp3HipError('conv_bn_act_conv1x1: the producers differ in their output size')
+            g32, b32 = ops._f32(gamma), ops._f32(beta)
+            check(lib.stp3_bn_finalize(stat.data_ptr(), c, count, ops._opt_ptr(g32), ops._opt_ptr(b32), eps, momentum,
+                                       ops._opt_ptr(rmean), ops._opt_ptr(rvar), stat.data_ptr() + 8 * c, stream), 'stp3_bn_finalize')
+            stats.append(stat)
+            params.append((g32, b32))
+            cfgs.append((c0, c, stride, pad, dil, cbias is not None, weight.dtype, None if cbias is None else cbias.dtype,
+                         None if gamma is None else gamma.dtype, None if beta is None else beta.dtype))
+            c0 += c
+        if n_prod == 1:
+            table = stats[0][2 * ctot:4 * ctot]                               # [scale | shift][C] as they lie
+        else:                                                                 # [scale of all | shift of all]: one launch
+            table = torch.cat([st[2 * c:3 * c] for st, c in zip(stats, couts)] + [st[3 * c:4 * c] for st, c in zip(stats, couts)])
+        w2b, _ = ops._bf16_weights(w2)
+        cout2 = w2b.shape[0]
+        fb2 = ops._f32(b2)
+        y = torch.empty((n, cout2, ho, wo), dtype=torch.bfloat16, device=dev, memory_format=torch.channels_last)
+        dims2 = _lib.ConvDims(n, ho, wo, ctot, ho, wo, cout2, 1, 1, 1, 0, 0, 1, 1, ctot, cout2, _lib.DTYPE_BF16, int(fb2 is not None))
+        check(lib.stp3_conv2d_fwd_pre(ctypes.byref(dims2), zbuf.data_ptr(), w2b.data_ptr(), ops._opt_ptr(fb2), table.data_ptr(),
+                                      int(act), y.data_ptr(), stream), 'stp3_conv2d_fwd_pre')
+        saved = [zbuf, table, w2b]
+        for x, wb, st, (g32, b32) in zip(xs, wbs, stats, params):
+            saved += [x, wb, st, g32, b32]
+        ctx.save_for_backward(*saved)
+        ctx.cfg = (int(act), n_prod, cfgs, count, w2.dtype, None if b2 is None else b2.dtype)
+        ctx.weight_refs = [ops.note_weight_use(w2)] + [ops.note_weight_use(p[1]) for p in prods]
+        ctx.weight_stamps = [ops.weight_stamp(w2)] + [ops.weight_stamp(p[1]) for p in prods]
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        saved = ctx.saved_tensors
+        zbuf, table, w2b = saved[:3]
+        act, n_prod, cfgs, count, w2dt, b2dt = ctx.cfg
+        for ref, stamp in zip(ctx.weight_refs, ctx.weight_stamps):
+            ops.check_weight_stamp(ref, stamp, 'conv_bn_act_conv1x1 backward')
+        lib = _lib.lib()
+        stream = ops._stream_handle()
+        dev = zbuf.device
+        n, ctot, ho, wo = zbuf.shape
+        # ---- the 1x1 layer (as ops._Conv2dMfma.backward; its operand is recomputed from z in the weight gradient's load) ----
+        cout_true = w2b.shape[0]
+        dy = dy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+        cpad = (-cout_true) % 8
+        if cpad:
+            dy = torch.nn.functional.pad(dy, (0, 0, 0, 0, 0, cpad)).contiguous(memory_format=torch.channels_last)
+            w2b = torch.nn.functional.pad(w2b, (0, 0, 0, 0, 0, 0, 0, cpad)).contiguous(memory_format=torch.channels_last)
+        ref2 = None if cpad else ctx.weight_refs[0]
+        db2 = None
+        if b2dt is not None and ctx.needs_input_grad[2]:
+            db2 = ops.channel_sums(dy)[:cout_true].to(b2dt)
+        da = ops.conv2d_data_grad(dy, w2b, ref2, (n, ctot, ho, wo), 1, (0, 0), (1, 1))     # gradient at the activation output
+        dw2 = None
+        if ctx.needs_input_grad[1]:
+            dw2 = ops._conv2d_wgrad(dy, zbuf, (cout_true + cpad, ctot, 1, 1), 1, (0, 0), (1, 1), leaf=ref2,
+                                    pre=(table, act))[:cout_true].to(w2dt)
+        # ---- per producer: BatchNorm backward from (d act, z), then the convolution backward (``_ConvBnAct.backward_steps``) ----
+        dzbuf = torch.empty_like(zbuf)                                                     # gradient at the convolution outputs
+        grads = []
+        for k, (c0, c, stride, pad, dil, has_cbias, wdt, cbdt, gdt, bdt) in enumerate(cfgs):
+            x, wb, stat, g32, b32 = saved[3 + 5 * k:8 + 5 * k]
+            base = 4 + _N_PRODUCER_ARGS * k
+            need = ctx.needs_input_grad[base:base + 5]
+            dak, zk, dconv = da[:, c0:c0 + c], zbuf[:, c0:c0 + c], dzbuf[:, c0:c0 + c]
+            dims = _lib.BnDims(n, ho * wo, c, ctot, ctot, c, _lib.DTYPE_BF16, act, ops.RES_NONE, 0, 0)
+            ws, ws_bytes = ops._bn_workspace(n, c, dev)
+            sumbuf = torch.empty((n + 1) * 3 * c, dtype=torch.float32, device=dev)
+            sums_off = n * 3 * c
+            mean_p, invstd_p = stat.data_ptr() + 16 * c, stat.data_ptr() + 20 * c
+            check(lib.stp3_bn_bwd_reduce(ctypes.byref(dims), dak.data_ptr(), zk.data_ptr(), None, None, None, mean_p, invstd_p,
+                                         ops._opt_ptr(g32), ops._opt_ptr(b32), ws.data_ptr(), ws_bytes, sumbuf.data_ptr(),
+                                         sumbuf.data_ptr() + 4 * sums_off, stream), 'stp3_bn_bwd_reduce')
+            lsums = sumbuf[sums_off:].view(3, c)
+            check(lib.stp3_bn_apply_bwd(ctypes.byref(dims), dak.data_ptr(), zk.data_ptr(), None, None, None, mean_p, invstd_p,
+                                        ops._opt_ptr(g32), ops._opt_ptr(b32), lsums.data_ptr(), count, dconv.data_ptr(), None,
+                                        stream), 'stp3_bn_apply_bwd')
+            dgamma = lsums[1].to(gdt) if gdt is not None and need[3] else None
+            dbeta = lsums[0].to(bdt) if bdt is not None and need[4] else None
+            cout, cin, kh, kw = wb.shape
+            ref = ctx.weight_refs[1 + k]
+            dx = dw = dcb = None
+            if need[0]:
+                dx = ops.conv2d_data_grad(dconv, wb, ref, x.shape, stride, pad, dil)
+            if need[1]:
+                dw = ops._conv2d_wgrad(dconv, x, (cout, cin, kh, kw), stride, pad, dil, leaf=ref).to(wdt)
+            if has_cbias and need[2]:
+                dcb = ops.channel_sums(dconv).to(cbdt)
+            grads += [dx, dw, dcb, dgamma, dbeta] + [None] * (_N_PRODUCER_ARGS - 5)
+        return (None, dw2, db2, None) + tuple(grads)
+
+
+def pre_fold_pays(n, h, w, channels):
+    """Is the normalised tensor (n, channels, h, w) that the fold would not store large enough (``PRE_FOLD_MIN_ELEMENTS``)?"""
+    return n * h * w * channels >= PRE_FOLD_MIN_ELEMENTS
+
+
+def pre_fold_supported(x, weight, stride, padding, dilation, w2):
+    """May conv(x, weight) -> BatchNorm -> activation -> conv1x1(w2) run as ``_ConvBnActConv1x1``?  (The caller has established
+    the fused conv -> BatchNorm operator's own conditions: training mode, GPU, bf16 kernels, the statistics epilogue's bound.)
+    Single process only (no statistics exchange inside), channel counts in whole 16-byte pieces on every side, a data gradient
+    the kernels can form (padding within the kernel's reach), operands the buffer-addressed staging takes (< 2 GiB)."""
+    if not PRE_FOLD or ops.replicas(None)[1]:
+        return False
+    cout, cin, kh, kw = weight.shape
+    p, d = ops._pair(padding), ops._pair(dilation)
+    if cout % 8 or cin % 8 or w2.shape[1] % 8 or tuple(w2.shape[2:]) != (1, 1) or cout > 4096:
+        return False
+    if d[0] * (kh - 1) - p[0] < 0 or d[1] * (kw - 1) - p[1] < 0:
+        return False
+    n, _, h, w = x.shape
+    return n * h * w * max(cin, w2.shape[1]) * 2 < (1 << 31)
+
+
+def conv_bn_act_conv1x1(producers, act, w2, b2):
+    """``producers``: [(x, conv weight, conv bias, BatchNorm module, stride, padding, dilation)] -> conv1x1(cat_k act(bn_k(conv_k(x_k))), w2)
+    + b2 through ``_ConvBnActConv1x1`` (see there; ``pre_fold_supported`` for every producer, sum of their channels = w2's)."""
+    flat = []
+    for x, weight, cbias, bn, stride, padding, dilation in producers:
+        if bn.num_batches_tracked is not None:
+            ops.bump_batch_counter(bn)
+        flat += [x, weight, cbias, bn.weight, bn.bias, bn.running_mean, bn.running_var, ops.bn_momentum(bn), float(bn.eps),
+                 ops._pair(stride)[0], ops._pair(padding), ops._pair(dilation)]
+    return _ConvBnActConv1x1.apply(int(act), w2, b2, len(producers), *flat)
+
+
 slot_view = ops.slot_view
 
 

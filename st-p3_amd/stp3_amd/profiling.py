@@ -45,7 +45,8 @@ def _conv_label(args):
             f' {d.Cin}->{d.Cout} @{d.Ho}x{d.Wo} x{d.N}')
 
 
-LABEL = {'stp3_conv2d_fwd': _conv_label, 'stp3_conv2d_fwd_add': _conv_label, 'stp3_conv2d_wgrad': _conv_label, 'stp3_conv2d_wgrad_partials': _conv_label}
+LABEL = {'stp3_conv2d_fwd': _conv_label, 'stp3_conv2d_fwd_add': _conv_label, 'stp3_conv2d_wgrad': _conv_label, 'stp3_conv2d_wgrad_partials': _conv_label,
+         'stp3_conv2d_fwd_pre': _conv_label, 'stp3_conv2d_wgrad_pre': _conv_label}
 
 
 def _bn_bytes(tensors):
@@ -80,7 +81,9 @@ WORK = {
     # (the expand convolution's data gradient inside the BatchNorm-backward apply pass of the recomputing route: counted with
     # the data gradient's flops and the WHOLE pass's time -- pessimistic for the family, never flattering)
     'stp3_conv2d_bn_bwd_apply_dx': ('conv_fwd_dgrad', _conv_flops),
+    'stp3_conv2d_fwd_pre': ('conv_fwd_dgrad', _conv_flops),                 # (a 1x1 layer with the BatchNorm apply pass in its operand load)
     'stp3_conv2d_wgrad': ('conv_wgrad', _conv_flops),
+    'stp3_conv2d_wgrad_pre': ('conv_wgrad', _conv_flops),
     'stp3_conv2d_wgrad_partials': ('conv_wgrad', _conv_flops),              # (the split contraction: all of the layer's flops)
     'stp3_conv2d_wgrad_reduce_batch': ('conv_wgrad', lambda args: 0.0),     # (their deferred sums, one launch per pass: time only)
     'stp3_bn_stats': ('batchnorm', _bn_bytes(1)),
