@@ -1150,6 +1150,30 @@ int stp3_dwconv2d_fwd_affine(const stp3_dwconv_dims* dims, const void* x, const 
                              void* y, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Streaming inference: the sliding window of the closed-loop forward (csrc/stp3_window.hip).  What it serves: the simulator
+ * tick, carla_agent.py:408-432 + :445 -- the newest camera frame joins a buffer of T and the model is handed the whole window
+ * again.  In eval mode the image encoder (stp3/models/encoder.py:57-97) couples no two images, so the encoder outputs of the
+ * T - 1 older frames are kept between ticks, in the layout stp3_lift_splat_fwd reads:
+ *   window [B][T][N * pixels][channels] float32, pixel-major (pixels = fH * fW) -- feat_pm and logits_pm.
+ * stp3_window_push advances up to STP3_WINDOW_JOBS_MAX such windows by one frame, IN PLACE, in ONE launch (`jobs` is a HOST
+ * array, it travels as the kernel argument): per sample  window[t] = window[t + 1]  for t < T - 1, then  window[T - 1] = src,
+ * the encoder head's new output -- a logical [B * N][channels][pixels] tensor of dtype STP3_DTYPE_F32 / _BF16 read through its
+ * three ELEMENT strides (NCHW-contiguous: pixels * channels, pixels, 1; channels-last: pixels * channels, 1, channels), every
+ * value widened exactly.  One thread owns one 16-byte channel vector position of the frame in all T frames, so the shift needs
+ * no second buffer and no order between workgroups; src must not overlap a window.
+ * STP3_EINVAL: B, T, N, pixels or channels < 1, a null pointer, a negative stride;  STP3_EUNSUP: channels % 4 != 0, a window
+ * that is not 16-byte aligned or holds 2^32 bytes or more, another dtype, more than STP3_WINDOW_JOBS_MAX jobs. */
+#define STP3_WINDOW_JOBS_MAX 4
+typedef struct stp3_window_job {
+    const void* src;            /* device: the newest frame, [B * N][channels][pixels] through the strides below */
+    float* window;              /* device: [B][T][N * pixels][channels] float32 */
+    int64_t stride_image, stride_channel, stride_pixel;     /* of src, in elements */
+    int32_t channels;
+    int32_t dtype;              /* STP3_DTYPE_* of src */
+} stp3_window_job;
+int stp3_window_push(int32_t B, int32_t T, int32_t N, int32_t pixels, int32_t n_jobs, const stp3_window_job* jobs, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Depth labels from LiDAR points (csrc/stp3_depth.hip): batch['depths'] of LIFT.GT_DEPTH.
  *
  * What is restated (the header of csrc/stp3_depth.hip gives the arithmetic):

@@ -184,6 +184,13 @@ class EvalPlanDims(ctypes.Structure):
                 [('traj_stride', ctypes.c_int64 * 2), ('gt_stride', ctypes.c_int64 * 2)])
 
 
+class WindowJob(ctypes.Structure):
+    """struct stp3_window_job (include/stp3_hip.h)."""
+    _fields_ = [('src', ctypes.c_void_p), ('window', ctypes.c_void_p), ('stride_image', ctypes.c_int64),
+                ('stride_channel', ctypes.c_int64), ('stride_pixel', ctypes.c_int64), ('channels', ctypes.c_int32),
+                ('dtype', ctypes.c_int32)]
+
+
 class OptimBucket(ctypes.Structure):
     """struct stp3_optim_bucket (include/stp3_hip.h)."""
     _fields_ = [('grad', ctypes.c_void_p), ('param', ctypes.c_void_p), ('exp_avg', ctypes.c_void_p),
@@ -194,6 +201,7 @@ DTYPE_F32 = 0
 DTYPE_BF16 = 1
 DEPTH_OUT_F32, DEPTH_OUT_F64, DEPTH_OUT_LABELS = 0, 1, 2
 
+WINDOW_JOBS_MAX = 4
 VOX_REFERENCE = 0
 VOX_PIXELMAJOR = 1
 BEV_CHANNELS_FIRST = 0
@@ -344,6 +352,7 @@ SIGNATURES = {
     'stp3_linear_fwd_affine': (c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32,
                                        c_void_p, c_void_p]),
     'stp3_dwconv2d_fwd_affine': (c_int, [_DW_P, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    'stp3_window_push': (c_int, [c_int32] * 5 + [ctypes.POINTER(WindowJob), c_void_p]),
 }
 
 _lib = None

@@ -25,6 +25,26 @@ conv -> BatchNorm -> activation layer makes two full passes over its tensor.  ``
   coefficient arena are rewritten in place -- the graph is not captured again;
 * a shape other than the captured one, a model in training mode and a model on the CPU raise ``Stp3HipError``.
 
+STREAMING.  The simulator tick is a sliding window (carla_agent.py:408-432): the newest camera frame joins a buffer and the model
+is handed all T = ``receptive_field`` frames again, T - 1 of which it encoded on the tick before.  In eval mode the image encoder
+couples no two images (BatchNorm on running statistics, squeeze-excite and the ASPP pooling per image, drop-connect off), while
+everything behind it depends on the whole window (past frames are re-aligned to the new present pose every tick).
+``StreamingEngine`` therefore caches exactly the encoder's two outputs, in the pixel-major float32 layout the voxel pool reads:
+
+    engine = StreamingEngine(model, example_batch, autocast_dtype=torch.bfloat16)     # example: the shapes of InferenceEngine's
+    out = engine.step(image_new, intrinsics, extrinsics, future_egomotion)            # (B, N, 3, H, W) + the WINDOW's poses
+
+* ``step`` copies the B * N newest images (a third of the window's), rebuilds the plan and the ego-motion vector in place and
+  replays ONE single-stream graph: the encoder on B * N images, ``ops.window_push`` (one launch: both caches advance by a frame
+  in place), the voxel pool on the caches, then ``STP3.forward_from_bev`` -- the plain forward's own tail;
+* it returns None while fewer than T frames were pushed since construction or ``reset()`` (the reference agent only buffers
+  during its first ticks as well), then the static output dict (``clone=True``: copies).  ``depth_prediction`` is a view of the
+  float32 logits cache (the plain forward returns the autocast dtype; equal after ``.float()``);
+* the encoder's kernels size their grids and partial sums from the problem, so B * N images and B * T * N images may round
+  differently: the outputs are BIT-EQUAL to ``model.eval()(...)`` with the encoder called per frame (B * N images at a time),
+  not to the full-window forward (tests/test_streaming_gpu.py prints the difference to the latter);
+* ``reset()`` zero-fills the caches and starts a new sequence, ``refresh()`` is ``InferenceEngine.refresh``; neither captures again.
+
 Any configuration whose eval forward is free of host synchronisation can be captured: Perception.yml (N_FUTURE_FRAMES = 0) and
 the prediction stage (eval mode samples with zero noise, models/stp3.py ``distribution_forward``).  The planner call that
 follows the forward stays with the caller, as in evaluate.py:121-132 (or ``ops_plan.plan_scene`` + ``Planning.drive``): captured behind
@@ -194,6 +214,111 @@ class InferenceEngine:
         self._ego_upload(future_egomotion.detach().float().cpu())
         self.graph.replay()
         self.replays += 1
+        if clone:
+            return {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.outputs.items()}
+        return self.outputs
+
+
+def streaming_tick(model, image, feat_window, logits_window, plan, ego):
+    """What ``StreamingEngine`` captures: the encoder on the newest frame's images (B, N, 3, H, W) -> ``ops.window_push`` -> the
+    voxel pool on the caches -> the plain forward's tail.  The caller provides ``torch.no_grad()``, the autocast and the
+    fused-eval scope."""
+    d = plan.dims
+    feat, depth = model.encoder(image.view(d.B * d.N, *image.shape[2:]))
+    ops.window_push([(feat, feat_window), (depth, logits_window)])
+    bev = ops.lift_splat_pm(feat_window, logits_window, plan, model.discount, model.bev_channels_last, model._bev_dtype())
+    # the two outputs the plain forward takes from the encoder's tensors: the present frame's front camera, and the depth
+    # logits of the whole window -- (B, T, N, D, fH, fW) over the cache's [B][T][N][fH][fW][D] memory
+    cam_front = model._cam_front(feat.view(d.B, 1, d.N, *feat.shape[1:]))
+    depth = logits_window.view(d.B, d.T, d.N, d.fH, d.fW, d.D).permute(0, 1, 2, 5, 3, 4)
+    return model.forward_from_bev(bev, depth, cam_front, ego)
+
+
+class StreamingEngine:
+    """See the module docstring (STREAMING).  ``example_batch`` as for ``InferenceEngine``: its image has at least
+    ``model.receptive_field`` frames, of which the engine takes B, N and the image size; its poses have the shapes every later
+    ``step`` hands in."""
+
+    def __init__(self, model, example_batch, autocast_dtype=torch.bfloat16, warmup=3):
+        if isinstance(example_batch, dict):
+            example_batch = tuple(example_batch[k] for k in _INPUTS)
+        image, intrinsics, extrinsics, ego = example_batch
+        self._check_model(model)
+        dev = next(model.parameters()).device
+        self.model, self.device, self.autocast_dtype = model, dev, autocast_dtype
+        t = self.frames = int(model.receptive_field)
+        if image.dim() != 6 or image.shape[1] < t:
+            raise Stp3HipError(f'StreamingEngine: the example image has shape {tuple(image.shape)}; (B, S >= {t}, N, 3, H, W) expected')
+        b, _, n, c, h, w = image.shape
+        # static inputs: the NEWEST frame's images on the device (a buffer of the engine's own); the window's camera poses stay
+        # on the host, its ego-motion vectors go to a device buffer refreshed per step -- as in InferenceEngine
+        self.image = torch.empty((b, n, c, h, w), dtype=image.dtype, device=dev)
+        self.image.copy_(image[:, t - 1])
+        self.ego = ego.detach().float().to(dev)
+        self._ego_upload = ops.PinnedUpload(self.ego)
+        self.pose_shapes = tuple(tuple(p.shape) for p in (intrinsics, extrinsics, ego))
+        self.plan = model.prepare_plan(intrinsics, extrinsics, ego, dev)
+        model.prebuilt_plan = None
+        # the window caches: what stp3_lift_splat_fwd reads, [B][T][N fH fW][C | D] float32
+        d = self.plan.dims
+        self.feat_window = torch.zeros((b, t, d.NPIX, d.C), dtype=torch.float32, device=dev)
+        self.logits_window = torch.zeros((b, t, d.NPIX, d.D), dtype=torch.float32, device=dev)
+        self.coefs = EvalCoefficients(model, dev) if autocast_dtype == torch.bfloat16 else None
+        self.gates = ops_pred.EngineGateWeights()
+        self.stream = torch.cuda.Stream(device=dev)            # warm-up AND capture: scratch buffers are per stream
+        cur = torch.cuda.current_stream(dev)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            for _ in range(warmup):
+                self._tick()
+        cur.wait_stream(self.stream)
+        torch.cuda.synchronize(dev)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=self.stream):
+            self.outputs = self._tick()
+        torch.cuda.synchronize(dev)
+        self.replays = 0
+        self.filled = 0
+        self.reset()                                           # (the warm-up ticks pushed the example frame)
+
+    def _tick(self):
+        auto = (torch.autocast('cuda', dtype=self.autocast_dtype) if self.autocast_dtype is not None
+                else contextlib.nullcontext())
+        scope = fused.eval_fusion(self.coefs, self.gates) if self.coefs is not None else contextlib.nullcontext()
+        with torch.no_grad(), auto, scope:
+            return streaming_tick(self.model, self.image, self.feat_window, self.logits_window, self.plan, self.ego)
+
+    def reset(self):
+        """Start a new sequence: zero-fill the caches; the next T - 1 steps return None.  The graph is not captured again."""
+        self.feat_window.zero_()
+        self.logits_window.zero_()
+        self.filled = 0
+
+    _check_model = staticmethod(InferenceEngine._check_model)
+    refresh = InferenceEngine.refresh                          # (reads self.model / device / gates / coefs: the same fields)
+
+    def step(self, image_new, intrinsics, extrinsics, future_egomotion, clone=False):
+        """One tick.  ``image_new``: the newest frame, (B, N, 3, H, W) or (B, 1, N, 3, H, W); the three pose tensors describe the
+        WHOLE current window (shapes of the example).  Returns None until T frames have been pushed, then the dict
+        ``STP3.forward`` returns: the engine's static outputs, OVERWRITTEN BY THE NEXT STEP -- ``clone=True`` returns copies."""
+        self._check_model(self.model, deep=False)
+        if image_new is not self.image:
+            shape = tuple(image_new.shape)
+            if shape != tuple(self.image.shape) and shape != (self.image.shape[0], 1) + tuple(self.image.shape[1:]):
+                raise Stp3HipError(f'StreamingEngine: image shape {shape} differs from the captured {tuple(self.image.shape)}')
+        shapes = tuple(tuple(p.shape) for p in (intrinsics, extrinsics, future_egomotion))
+        if shapes != self.pose_shapes:
+            raise Stp3HipError(f'StreamingEngine: pose shapes {shapes} differ from the captured {self.pose_shapes}')
+        if image_new is not self.image:
+            self.image.copy_(image_new.reshape(self.image.shape), non_blocking=True)
+        self.plan = self.model.prepare_plan(intrinsics, extrinsics, future_egomotion, self.device, out=self.plan)
+        self.model.prebuilt_plan = None
+        self._ego_upload(future_egomotion.detach().float().cpu())
+        self.graph.replay()
+        self.replays += 1
+        self.filled = min(self.filled + 1, self.frames)
+        if self.filled < self.frames:
+            return None
         if clone:
             return {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.outputs.items()}
         return self.outputs

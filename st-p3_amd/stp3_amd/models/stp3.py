@@ -202,6 +202,13 @@ class STP3(nn.Module):
         future_egomotion = future_egomotion[:, :rf].contiguous()
 
         x, depth, cam_front = self.calculate_birds_eye_view_features(image, intrinsics, extrinsics, future_egomotion)
+        return self.forward_from_bev(x, depth, cam_front, future_egomotion)
+
+    def forward_from_bev(self, x, depth, cam_front, future_egomotion):
+        """Everything behind ``calculate_birds_eye_view_features``: temporal model, prediction stage, decoder.  ``forward`` ends
+        here; ``inference.StreamingEngine`` enters here with BEV features pooled from its cached encoder outputs.
+        ``future_egomotion``: (B, S >= receptive_field, 6); only its first receptive_field - 1 frames are read."""
+        rf = self.receptive_field
         output = {'depth_prediction': depth, 'cam_front': cam_front}
 
         if self.cfg.MODEL.TEMPORAL_MODEL.INPUT_EGOPOSE:

@@ -418,6 +418,50 @@ def lift_splat(feat, depth_logits, lift_plan, discount, channels_last=False, out
                             out_dtype == torch.bfloat16)
 
 
+def lift_splat_pm(feat_pm, logits_pm, lift_plan, discount, channels_last=False, out_dtype=torch.float32):
+    """``lift_splat`` on tensors that already ARE pixel-major float32 -- feat_pm (B,T,N*fH*fW,C), logits_pm (B,T,N*fH*fW,D),
+    contiguous: the window caches of the streaming engine (``window_push``).  No cast, no re-layout, the same kernels."""
+    d = lift_plan.dims
+    return _LiftSplat.apply(feat_pm.view(d.BT, d.NPIX, d.C), logits_pm.view(d.BT, d.NPIX, d.D), lift_plan, float(discount),
+                            bool(channels_last), out_dtype == torch.bfloat16)
+
+
+def window_push(pairs):
+    """Advance sliding windows of encoder outputs by one frame, in place, in ONE launch (csrc/stp3_window.hip).
+
+    ``pairs``: up to ``_lib.WINDOW_JOBS_MAX`` (new, window) with ``window`` (B,T,N*fH*fW,C) float32 contiguous -- what
+    ``lift_splat_pm`` reads -- and ``new`` the encoder head's output for the newest frame, logical (B*N,C,fH,fW), bf16 or float32,
+    NCHW-contiguous or channels-last memory.  Per sample frame t takes frame t+1 and frame T-1 the new values: the ones
+    ``lift_splat`` makes with ``.float().permute(...).reshape(...)``.  All pairs share B, T, N and fH*fW."""
+    if not pairs:
+        return
+    for new, window in pairs:                                      # ranks first: everything below indexes the shapes
+        if new.dim() != 4 or window.dim() != 4:
+            raise _lib.Stp3HipError(f'window_push: a frame (B*N,C,fH,fW) and a window (B,T,N*fH*fW,C) are expected, got '
+                                    f'{tuple(new.shape)} and {tuple(window.shape)}')
+    first_new, first_window = pairs[0]
+    b, t = int(first_window.shape[0]), int(first_window.shape[1])
+    n, pixels = int(first_new.shape[0]) // max(b, 1), int(first_new.shape[2]) * int(first_new.shape[3])
+    jobs = (_lib.WindowJob * len(pairs))()
+    for job, (new, window) in zip(jobs, pairs):
+        _need_gpu(new, window)
+        c = int(new.shape[1])
+        if (window.dtype != torch.float32 or not window.is_contiguous() or tuple(window.shape) != (b, t, n * pixels, c)
+                or tuple(new.shape[:1]) != (b * n,) or int(new.shape[2]) * int(new.shape[3]) != pixels):
+            raise _lib.Stp3HipError(f'window_push: window {tuple(window.shape)} {window.dtype} does not hold frames of '
+                                    f'{tuple(new.shape)} for {b} samples')
+        if new.dtype not in (torch.float32, torch.bfloat16):
+            raise _lib.Stp3HipError(f'window_push: {new.dtype} frames are not supported (float32 / bfloat16)')
+        if new.shape[2] > 1 and new.stride(2) != new.shape[3] * new.stride(3):
+            raise _lib.Stp3HipError('window_push: the rows of the new frame are not evenly spaced (one pixel stride is needed)')
+        job.src, job.window = new.data_ptr(), window.data_ptr()
+        job.stride_image, job.stride_channel, job.stride_pixel = new.stride(0), new.stride(1), new.stride(3)
+        job.channels, job.dtype = c, _lib.DTYPE_BF16 if new.dtype == torch.bfloat16 else _lib.DTYPE_F32
+    with _timed('window_push'):
+        rc = _lib.lib().stp3_window_push(b, t, n, pixels, len(pairs), jobs, _stream())
+    check(rc, 'stp3_window_push')
+
+
 # ----------------------------------------------------------------------------------------------
 # stand-alone voxel summing (compatibility with the reference's operator boundary)
 # ----------------------------------------------------------------------------------------------
