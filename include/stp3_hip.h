@@ -1243,6 +1243,67 @@ int stp3_depth_labels_from_lidar(const stp3_depth_dims* dims, const float* point
                                  int64_t* labels, void* stream);
 int stp3_depth_from_maps(const stp3_depth_dims* dims, const void* maps, int32_t map_dtype, void* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The training video (csrc/stp3_vis.hip): stp3/utils/visualisation.py:208-322 (visualise_output) of ONE sample, painted on the
+ * device.  video [T][3][7 H][2 W] uint8, planar; rows of panels top to bottom: instance, future flow, segmentation,
+ * centerness, offset, pedestrian, planning; left column labels, right column predictions.  Every panel shows cell
+ * (H - 1 - r, W - 1 - c) at its pixel (r, c) and, when enabled, carries a one-pixel black border; a disabled panel is zero.
+ * The arithmetic of every panel is stated in the header of csrc/stp3_vis.hip; the planning panel is this project's own
+ * (DESIGN.md section 4.15), everything else is the reference's byte for byte up to the rounding of atan2.
+ *
+ * A source (stp3_vis_map) is the map of frame 0 of the sample with strides in ELEMENTS: frames, channels, rows, columns.
+ * [0] of every pair belongs to the labels, [1] to the predictions.
+ *   seg, ped      labels: int64 (1 is the class that is drawn); predictions: float32 | bf16 logits of 2 channels, class 1 where
+ *                 logit[1] > logit[0]
+ *   inst          int64 instance ids (labels; the consistent ids of the instance post-processing)
+ *   center        float32 | bf16, 1 channel;   offset, flow: float32 | bf16, 2 channels
+ *   plan          hdmap: labels int64 values of 2 channels, predictions float32 | bf16 logits of 4 channels (two pairs);
+ *                 traj: n_points float32 (x, y) in metres
+ *   ego_cells     [n_ego][2] int32 (row, column) of the ego box;   dx / bx: resolution and first cell centre of rows and columns
+ *   palette [70][3], jet [256][3], wheel [55][3]: uint8 colour tables (stp3_amd/visualisation.py owns them)
+ * stp3_vis_render enqueues two kernels on `stream` -- one that copies the descriptor into `workspace` (stp3_vis_workspace_bytes,
+ * 8-byte aligned) and, with STP3_VIS_INSTANCE, computes the per-frame scalars there (min / max of the two centre maps, smallest
+ * id of the two instance maps: one workgroup per scalar pair), then the painter -- allocates nothing, does not synchronise and is
+ * deterministic (no floating-point atomics).
+ * STP3_EINVAL: null descriptor / video / workspace / required source, T < 1, H or W < 3, unknown dtype, n_points or n_ego < 0;
+ * STP3_EUNSUP: 2 W * 7 H * 3 * T >= 2^31 or 7 T > 65535. */
+#define STP3_VIS_DTYPE_I64 2            /* beside STP3_DTYPE_F32 / STP3_DTYPE_BF16 */
+#define STP3_VIS_INSTANCE     1        /* instance, centerness and offset rows */
+#define STP3_VIS_FLOW         2
+#define STP3_VIS_PEDESTRIAN   4
+#define STP3_VIS_PLAN_LABELS  8
+#define STP3_VIS_PLAN_PRED   16
+
+typedef struct stp3_vis_map {
+    const void* ptr;
+    int64_t stride_t, stride_c, stride_h, stride_w;
+    int32_t dtype, reserved;
+} stp3_vis_map;
+
+typedef struct stp3_vis_plan {
+    const void* hdmap;
+    int64_t hd_stride_c, hd_stride_h, hd_stride_w;
+    const float* traj;
+    int64_t traj_stride_p, traj_stride_c;
+    int32_t hd_dtype, n_points;
+} stp3_vis_plan;
+
+typedef struct stp3_vis_desc {
+    int32_t T, H, W, panels;
+    stp3_vis_map seg[2], ped[2], inst[2], center[2], offset[2], flow[2];
+    stp3_vis_plan plan[2];
+    const int32_t* ego_cells;
+    const uint8_t* palette;
+    const uint8_t* jet;
+    const uint8_t* wheel;
+    int32_t n_ego;
+    float dx0, dx1, bx0, bx1;
+    int32_t reserved;
+} stp3_vis_desc;
+
+int stp3_vis_workspace_bytes(const stp3_vis_desc* desc, size_t* bytes);
+int stp3_vis_render(const stp3_vis_desc* desc, uint8_t* video, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -197,8 +197,31 @@ class OptimBucket(ctypes.Structure):
                 ('exp_avg_sq', ctypes.c_void_p), ('numel', ctypes.c_int64), ('first_block', ctypes.c_int64)]
 
 
+class VisMap(ctypes.Structure):
+    """struct stp3_vis_map (include/stp3_hip.h)."""
+    _fields_ = ([('ptr', ctypes.c_void_p)] + [(k, ctypes.c_int64) for k in ('stride_t', 'stride_c', 'stride_h', 'stride_w')] +
+                [('dtype', ctypes.c_int32), ('reserved', ctypes.c_int32)])
+
+
+class VisPlan(ctypes.Structure):
+    """struct stp3_vis_plan (include/stp3_hip.h)."""
+    _fields_ = ([('hdmap', ctypes.c_void_p)] + [(k, ctypes.c_int64) for k in ('hd_stride_c', 'hd_stride_h', 'hd_stride_w')] +
+                [('traj', ctypes.c_void_p), ('traj_stride_p', ctypes.c_int64), ('traj_stride_c', ctypes.c_int64),
+                 ('hd_dtype', ctypes.c_int32), ('n_points', ctypes.c_int32)])
+
+
+class VisDesc(ctypes.Structure):
+    """struct stp3_vis_desc (include/stp3_hip.h)."""
+    _fields_ = ([(k, ctypes.c_int32) for k in ('T', 'H', 'W', 'panels')] +
+                [(k, VisMap * 2) for k in ('seg', 'ped', 'inst', 'center', 'offset', 'flow')] + [('plan', VisPlan * 2)] +
+                [(k, ctypes.c_void_p) for k in ('ego_cells', 'palette', 'jet', 'wheel')] + [('n_ego', ctypes.c_int32)] +
+                [(k, ctypes.c_float) for k in ('dx0', 'dx1', 'bx0', 'bx1')] + [('reserved', ctypes.c_int32)])
+
+
 DTYPE_F32 = 0
 DTYPE_BF16 = 1
+VIS_DTYPE_I64 = 2
+VIS_INSTANCE, VIS_FLOW, VIS_PEDESTRIAN, VIS_PLAN_LABELS, VIS_PLAN_PRED = 1, 2, 4, 8, 16
 DEPTH_OUT_F32, DEPTH_OUT_F64, DEPTH_OUT_LABELS = 0, 1, 2
 
 WINDOW_JOBS_MAX = 4
@@ -353,6 +376,8 @@ SIGNATURES = {
                                        c_void_p, c_void_p]),
     'stp3_dwconv2d_fwd_affine': (c_int, [_DW_P, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     'stp3_window_push': (c_int, [c_int32] * 5 + [ctypes.POINTER(WindowJob), c_void_p]),
+    'stp3_vis_workspace_bytes': (c_int, [ctypes.POINTER(VisDesc), ctypes.POINTER(c_size_t)]),
+    'stp3_vis_render': (c_int, [ctypes.POINTER(VisDesc), c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

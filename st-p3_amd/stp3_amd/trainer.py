@@ -92,6 +92,9 @@ class TrainingModule(nn.Module):
             self.model.planning_weight = _scalar()
         self.training_step_count = 0
         self._fused_terms = None
+        # what Lightning attaches in the reference: ``logger.experiment`` is a tensorboard SummaryWriter.  None: nothing is logged
+        # and the steps never render the video
+        self.logger = None
 
     # ------------------------------------------------------------------------------------------
     def _weighted(self, loss, name, key, value):
@@ -319,13 +322,29 @@ class TrainingModule(nn.Module):
             labels['flow'] = self._warp_pair(batch['flow'], ego, rf, False)
         return labels
 
+    def visualise(self, labels, output, batch_idx, prefix='train'):
+        """The video of sample 0 (``visualisation.visualise_output``: (1, T, 3, 7 H, 2 W) uint8 on the tensors' device), handed to
+        ``logger.experiment.add_video`` under the reference's names when a logger is attached (trainer.py:362-367)."""
+        from .visualisation import visualise_output
+        video = visualise_output(labels, output, self.cfg)
+        name = f'{prefix}_outputs'
+        if prefix == 'val':
+            name = name + f'_{batch_idx}'
+        if self.logger is not None:
+            self.logger.experiment.add_video(name, video, global_step=self.training_step_count, fps=2)
+        return video
+
     def training_step(self, batch, batch_idx=0):
-        _, _, loss = self.shared_step(batch, True, fused_total=True)
+        output, labels, loss = self.shared_step(batch, True, fused_total=True)
         self.training_step_count += 1
+        if self.logger is not None and self.training_step_count % self.cfg.VIS_INTERVAL == 0:      # trainer.py:374
+            self.visualise(labels, output, batch_idx, prefix='train')
         return loss['total']
 
     def validation_step(self, batch, batch_idx=0):
         output, labels, _ = self.shared_step(batch, False)
+        if self.logger is not None and batch_idx == 0:                                               # trainer.py:387
+            self.visualise(labels, output, batch_idx, prefix='val')
         return {'step_val_seg_iou_dynamic': self.metric_vehicle_val.compute()[1]}
 
     # ------------------------------------------------------------------------------------------
