@@ -2,7 +2,7 @@
 
 A step of BASELINE configs[2] is ~1 900 kernel launches of 5-100 us; launched eagerly the Python side of the step costs
 31-39 ms against 39-40 ms of GPU time: the host is the wall the kernels run into.  Every shape in the
-step is static, no operator reads a value back, every scratch buffer is owned by an operator -- so forward, backward,
+step is static, no operator reads a value back, scratch buffers keep their addresses (scratch.py) -- so forward, backward,
 gradient gather, clipping, Adam and the refresh of the bf16 weight shadows are captured ONCE and replayed per batch.  The
 captured step is a single stream (with a prepared plan the forward forks no side stream): a multi-stream form of the step --
 the encoder's two heads on two streams, the weight gradients of leaf parameters beside the data gradients -- was built and
@@ -32,7 +32,7 @@ was available to any round, so no scaling curve has been measured.
 """
 import torch
 
-from . import ops
+from . import capture, ops
 
 _POSE_KEYS = ('intrinsics', 'extrinsics', 'future_egomotion')
 
@@ -58,15 +58,7 @@ class GraphedTrainStep:
         # fresh nodes under the capture stream.
         import gc
         gc.collect()
-        self.stream = torch.cuda.Stream(device=dev)            # warm-up AND capture: scratch buffers are per stream
-        cur = torch.cuda.current_stream(dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            for i in range(warmup):
-                self._body()
-                log(f'graph: eager warm-up {i} done')
-        cur.wait_stream(self.stream)
-        torch.cuda.synchronize(dev)
+        self.stream = capture.warm_up(self._body, dev, warmup, log)
         if buckets.exchange:
             # The process group's watchdog thread polls the events of the collectives the warm-up steps enqueued until it has
             # seen them complete (one pass every 100 ms); a poll that lands inside the capture fails with
@@ -76,15 +68,12 @@ class GraphedTrainStep:
             import time
             time.sleep(1.0)
         ops.flush_batch_counters()
-        self.graph = torch.cuda.CUDAGraph()
         # (with collectives in the step the process group's watchdog thread polls events of EARLIER work while this thread
         # captures: `relaxed` keeps that legal -- the default mode fails the capture on any such call from any thread; ROCm 7.2
         # does not start a `thread_local` capture at all: capture_begin trips over an inactive capture status, r06c)
         mode = 'relaxed' if buckets.exchange else 'global'
         exchanges0, reductions0 = ops.exchange_counts()['batchnorm'], buckets.reductions_launched
-        with torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode=mode):
-            self.loss = self._body()
-        torch.cuda.synchronize(dev)
+        self.graph, self.loss = capture.capture(self._body, self.stream, dev, mode)
         # the collectives ONE replay issues (counted where they were recorded: the host does not see them again)
         self.collectives = {'batchnorm_statistics_all_reduces': ops.exchange_counts()['batchnorm'] - exchanges0,
                             'gradient_bucket_all_reduces': buckets.reductions_launched - reductions0}

@@ -55,7 +55,7 @@ import contextlib
 import torch
 import torch.nn as nn
 
-from . import _lib, ops, ops_pred
+from . import _lib, capture, ops, ops_pred
 from ._lib import Stp3HipError
 from .layers import fused
 
@@ -154,18 +154,8 @@ class InferenceEngine:
         self.coefs = EvalCoefficients(model, dev) if autocast_dtype == torch.bfloat16 else None
         # the merged gate weights of the prediction stage's GRU cells (bf16 path only): buffers refresh() rewrites in place
         self.gates = ops_pred.EngineGateWeights()
-        self.stream = torch.cuda.Stream(device=dev)            # warm-up AND capture: scratch buffers are per stream
-        cur = torch.cuda.current_stream(dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            for _ in range(warmup):
-                self._forward()
-        cur.wait_stream(self.stream)
-        torch.cuda.synchronize(dev)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=self.stream):
-            self.outputs = self._forward()
-        torch.cuda.synchronize(dev)
+        self.stream = capture.warm_up(self._forward, dev, warmup)
+        self.graph, self.outputs = capture.capture(self._forward, self.stream, dev)
         self.replays = 0
 
     @staticmethod
@@ -265,18 +255,8 @@ class StreamingEngine:
         self.logits_window = torch.zeros((b, t, d.NPIX, d.D), dtype=torch.float32, device=dev)
         self.coefs = EvalCoefficients(model, dev) if autocast_dtype == torch.bfloat16 else None
         self.gates = ops_pred.EngineGateWeights()
-        self.stream = torch.cuda.Stream(device=dev)            # warm-up AND capture: scratch buffers are per stream
-        cur = torch.cuda.current_stream(dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            for _ in range(warmup):
-                self._tick()
-        cur.wait_stream(self.stream)
-        torch.cuda.synchronize(dev)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=self.stream):
-            self.outputs = self._tick()
-        torch.cuda.synchronize(dev)
+        self.stream = capture.warm_up(self._tick, dev, warmup)
+        self.graph, self.outputs = capture.capture(self._tick, self.stream, dev)
         self.replays = 0
         self.filled = 0
         self.reset()                                           # (the warm-up ticks pushed the example frame)

@@ -18,7 +18,7 @@ import weakref
 
 import torch
 
-from . import _lib
+from . import _lib, scratch
 from ._lib import LiftDims, VOX_PIXELMAJOR, VOX_REFERENCE, check
 
 
@@ -28,15 +28,6 @@ def _ptr(t):
 
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ws_key(device):
-    """Key of a scratch buffer: one per device AND stream -- operators of independent branches are queued on different HIP
-    streams (the encoder's two heads, the weight gradients beside the data gradients) and must not share scratch."""
-    device = torch.device(device)
-    if device.type != 'cuda':
-        return device
-    return (device, torch.cuda.current_stream().cuda_stream)
 
 
 def _stream_handle():
@@ -319,21 +310,14 @@ def depth_softmax(dims, logits_pm):
 
 
 BEV_CHANNELS_FIRST, BEV_CHANNELS_LAST = _lib.BEV_CHANNELS_FIRST, _lib.BEV_CHANNELS_LAST
-_WORKSPACE = {}
 
 
 def lift_workspace(dims, device):
-    """Scratch of the pooling calls (one buffer per device, grown on demand): the run slots of the forward, the
-    voxel-major gradient G_t of the backward and, for the reference (channels-first) layout, the channels-last BEV
-    before the transpose pass."""
+    """Scratch of the pooling calls (``scratch.get``): the run slots of the forward, the voxel-major gradient G_t of the
+    backward and, for the reference (channels-first) layout, the channels-last BEV before the transpose pass."""
     nbytes = ctypes.c_size_t()
     check(_lib.lib().stp3_lift_workspace_bytes(ctypes.byref(dims), ctypes.byref(nbytes)), 'stp3_lift_workspace_bytes')
-    key = _ws_key(device)
-    ws = _WORKSPACE.get(key)
-    if ws is None or ws.numel() < nbytes.value:
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=torch.device(device))
-        _WORKSPACE[key] = ws
-    return ws, nbytes.value
+    return scratch.get('lift', nbytes.value, device), nbytes.value
 
 
 class _LiftSplat(torch.autograd.Function):
@@ -734,19 +718,13 @@ def bump_batch_counter(bn):
 ACT_NONE, ACT_RELU, ACT_SWISH = _lib.ACT_NONE, _lib.ACT_RELU, _lib.ACT_SWISH
 RES_NONE, RES_BEFORE_ACT, RES_AFTER_ACT = _lib.RES_NONE, _lib.RES_BEFORE_ACT, _lib.RES_AFTER_ACT
 
-_BN_WORKSPACE = {}
 _BN_MAX_ROW_BLOCKS = 128          # STP3_BN_MAX_ROW_BLOCKS
 
 
 def _bn_workspace(n, c, device):
-    """Scratch of the two-stage reductions: N * 128 * 3 * C floats at most (one buffer per device, grown on demand)."""
+    """Scratch of the two-stage reductions: N * 128 * 3 * C floats at most (``scratch.get``)."""
     need = n * _BN_MAX_ROW_BLOCKS * 3 * c * 4
-    key = _ws_key(device)
-    ws = _BN_WORKSPACE.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 8 << 20), dtype=torch.uint8, device=device)
-        _BN_WORKSPACE[key] = ws
-    return ws, need
+    return scratch.get('bn', need, device, floor=8 << 20), need
 
 
 def _rows_view(t):
@@ -1293,9 +1271,6 @@ def _conv_out(size, k, stride, pad, dil):
     return (size + 2 * pad - dil * (k - 1) - 1) // stride + 1
 
 
-_CONV_STAT_WS = {}
-
-
 class SkipCarrier:
     """The gradient of a block's identity skip, handed from the operator that adds the skip (the BatchNorm at the block's end:
     its backward runs first and stores the gradient here instead of returning it) to the operator that consumes the block
@@ -1338,12 +1313,7 @@ def _conv2d_launch(x, wb, bias, stride, pad, dil, out_dtype, sums_ptr=None, out_
     if sums_ptr is not None:
         nbytes = ctypes.c_size_t()
         check(lib.stp3_conv2d_fwd_workspace(ctypes.byref(dims), ctypes.byref(nbytes)), 'stp3_conv2d_fwd_workspace')
-        key = _ws_key(x.device)
-        ws = _CONV_STAT_WS.get(key)
-        if ws is None or ws.numel() < nbytes.value:
-            ws = torch.empty(max(nbytes.value, 8 << 20), dtype=torch.uint8, device=x.device)
-            _CONV_STAT_WS[key] = ws
-        ws_ptr, ws_bytes = ws.data_ptr(), nbytes.value
+        ws_ptr, ws_bytes = scratch.get('conv_stat', nbytes.value, x.device, floor=8 << 20).data_ptr(), nbytes.value
     if add is not None:
         # y = conv + add in the kernel's epilogue (the skip's gradient joins the data gradient where it is written)
         assert sums_ptr is None
@@ -1359,9 +1329,6 @@ def _conv2d_launch(x, wb, bias, stride, pad, dil, out_dtype, sums_ptr=None, out_
     check(lib.stp3_conv2d_fwd(ctypes.byref(dims), _ptr(x), _ptr(wb), _opt_ptr(bias), _ptr(y), sums_ptr, ws_ptr, ws_bytes,
                               _stream()), 'stp3_conv2d_fwd')
     return y
-
-
-_CONV_WORKSPACE = {}
 
 
 # Weight gradients of LEAF parameters are written straight into the parameter's slice of its flat gradient bucket
@@ -1413,10 +1380,10 @@ def _conv2d_wgrad(dy, x, wshape, stride, pad, dil, leaf=None, pre=None):
         # pass (``_WeightShadows.scatter``) cuts every such buffer into the parameters' bucket slices
         dw = asm['dw'].detach()
         direct = True
-    key = _ws_key(x.device)
     if direct and DEFER_WGRAD_REDUCE and getattr(leaf, '_stp3_uses', 0) == 1 and _single_process():
         # nobody reads this gradient before the optimizer: only the split contraction runs now, its partial sums stay in this
         # layer's slice of the arena, and ``flush_wgrad_reductions`` (GradientBuckets.finish) sums all layers' in one launch
+        key = scratch.key(x.device)
         arena = _WGRAD_ARENAS.get(key)
         if arena is None:
             arena = _WGRAD_ARENAS[key] = _WgradArena(x.device)
@@ -1428,10 +1395,7 @@ def _conv2d_wgrad(dy, x, wshape, stride, pad, dil, leaf=None, pre=None):
                   'stp3_conv2d_wgrad_partials')
             arena.jobs.append((slot, dw.data_ptr(), cout * cin * kh * kw, splits.value))
             return dw
-    ws = _CONV_WORKSPACE.get(key)
-    if ws is None or ws.numel() < nbytes.value:
-        ws = torch.empty(max(nbytes.value, 64 << 20), dtype=torch.uint8, device=x.device)
-        _CONV_WORKSPACE[key] = ws
+    ws = scratch.get('conv_wgrad', nbytes.value, x.device, floor=64 << 20)
     if pre is not None:
         check(lib.stp3_conv2d_wgrad_pre(ctypes.byref(dims), _ptr(dy), _ptr(x), pre_ptr, pre_act, _ptr(dw), _ptr(ws),
                                         ctypes.c_size_t(nbytes.value), _stream()), 'stp3_conv2d_wgrad_pre')
@@ -1465,13 +1429,14 @@ def _single_process():
 class _WgradArena:
     """Partial sums of the deferred weight gradients of one backward pass: a bump allocator over one device buffer.  A pass that
     needs more than the buffer holds takes the immediate path for the layers that do not fit and the buffer grows BETWEEN
-    passes (never while partials are live); the same sequence of layers gets the same addresses in every pass, which is what
-    a captured step needs."""
+    passes (never while partials are live, never while capturing); the same sequence of layers gets the same addresses in
+    every pass, which is what a captured step needs.  The buffer is ``scratch``'s, which keeps an outgrown one that a captured
+    step may still name."""
 
     def __init__(self, device):
         self.device = device
-        self.buf = torch.empty(64 << 20, dtype=torch.uint8, device=device)
-        self.retired = []              # outgrown buffers stay allocated: a captured step may still name their addresses
+        self.buf = None
+        self.size = 0                  # what the passes so far wanted (grown by ``flush``)
         self.used = 0
         self.wanted = 0
         self.jobs = []
@@ -1479,6 +1444,8 @@ class _WgradArena:
     def take(self, nbytes):
         nbytes = (nbytes + 255) // 256 * 256
         self.wanted += nbytes
+        if self.used == 0:             # a new pass, on the stream this arena is keyed by
+            self.buf = scratch.get('wgrad_arena', 0 if scratch.capturing() else self.size, self.device, floor=64 << 20)
         if self.used + nbytes > self.buf.numel():
             return None
         ptr = self.buf.data_ptr() + self.used
@@ -1491,11 +1458,9 @@ class _WgradArena:
             for rec, (partials, dw, numel, splits) in zip(arr, self.jobs):
                 rec.partials, rec.dw, rec.numel, rec.splits = partials, dw, numel, splits
             check(_lib.lib().stp3_conv2d_wgrad_reduce_batch(len(self.jobs), arr, _stream()), 'stp3_conv2d_wgrad_reduce_batch')
-        grow = self.wanted > self.buf.numel() and not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
-        self.jobs, self.used, wanted, self.wanted = [], 0, self.wanted, 0
-        if grow:
-            self.retired.append(self.buf)
-            self.buf = torch.empty(wanted + (wanted >> 3), dtype=torch.uint8, device=self.device)
+        if self.wanted > self.buf.numel() and not scratch.capturing():
+            self.size = self.wanted + (self.wanted >> 3)           # (taken by the next pass's first ``take``)
+        self.jobs, self.used, self.wanted = [], 0, 0
 
 
 def flush_wgrad_reductions():

@@ -16,21 +16,11 @@ import os
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, scratch
 from ._lib import check
 
-_WS = {}
 # the gate's two fully-connected layers through stp3_se_mlp_fwd / _bwd (one launch forward, one backward)
 _SE_MLP = True
-
-
-def _workspace(nbytes, device):
-    key = ops._ws_key(device)                 # per device and stream (ops._ws_key)
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(nbytes, 32 << 20), dtype=torch.uint8, device=device)
-        _WS[key] = ws
-    return ws
 
 
 def conv2d_v2(x, wb, bias, stride, pad, dil, sums_ptr=None):
@@ -231,7 +221,7 @@ class _PointwiseBnAct(torch.autograd.Function):
         dims = _lib.ConvDims(n, h, w, cin, h, w, cout, 1, 1, 1, 0, 0, 1, 1, ldx, cout, _lib.DTYPE_BF16, 0)
         need = ctypes.c_size_t()
         check(lib.stp3_conv2d_fwd_workspace(ctypes.byref(dims), ctypes.byref(need)), 'stp3_conv2d_fwd_workspace')
-        ws = _workspace(need.value, dev)
+        ws = scratch.get('fused', need.value, dev, floor=32 << 20)
         stat = torch.empty(6 * cout, dtype=torch.float32, device=dev)       # sum | sum of squares | scale | shift | mean | invstd
         stream = ops._stream_handle()
         check(lib.stp3_conv2d_fwd_stats(ctypes.byref(dims), x.data_ptr(), wb.data_ptr(), stat.data_ptr(), ws.data_ptr(),
@@ -270,7 +260,7 @@ class _PointwiseBnAct(torch.autograd.Function):
         dz, ldz = ops._rows_view(dz)
         if ldz % 8 or dz.data_ptr() % 16:
             dz, ldz = dz.contiguous(memory_format=torch.channels_last), cout
-        ws = _workspace(ws_bytes, dev)
+        ws = scratch.get('fused', ws_bytes, dev, floor=32 << 20)
         stream = ops._stream_handle()
         lsums = torch.empty(2, cout, dtype=torch.float32, device=dev)        # sum g (dbeta) | sum g * xhat (dgamma)
         check(lib.stp3_conv2d_bn_bwd_reduce(ctypes.byref(dims), x.data_ptr(), wb.data_ptr(), dz.data_ptr(), ldz, coef.data_ptr(),
@@ -666,7 +656,7 @@ def _se_pool(x, dims, dy=None):
     lib = _lib.lib()
     nbytes = ctypes.c_size_t()
     check(lib.stp3_se_workspace_bytes(ctypes.byref(dims), ctypes.byref(nbytes)), 'stp3_se_workspace_bytes')
-    ws = _workspace(nbytes.value, x.device)
+    ws = scratch.get('fused', nbytes.value, x.device, floor=32 << 20)
     out = torch.empty(dims.N, dims.C, dtype=torch.float32, device=x.device)
     check(lib.stp3_se_pool(ctypes.byref(dims), x.data_ptr(), ops._opt_ptr(dy), ws.data_ptr(), nbytes.value, out.data_ptr(),
                            ops._stream_handle()), 'stp3_se_pool')
@@ -822,7 +812,7 @@ class _DwBnSe(torch.autograd.Function):
         need2 = ctypes.c_size_t()
         check(lib.stp3_mbconv_workspace_bytes(ctypes.byref(sd), ctypes.byref(need2)), 'stp3_mbconv_workspace_bytes')
         ws_bytes = max(need.value, need2.value)
-        ws = _workspace(ws_bytes, dev)
+        ws = scratch.get('fused', ws_bytes, dev, floor=32 << 20)
         stream = ops._stream_handle()
         stat = torch.empty(6 * c, dtype=torch.float32, device=dev)        # sum | sum of squares | scale | shift | mean | invstd
         count = float(n * ho * wo)
@@ -876,7 +866,7 @@ class _DwBnSe(torch.autograd.Function):
         if da.dtype != e2.dtype:
             da = da.to(e2.dtype)
         da = da.contiguous(memory_format=torch.channels_last)
-        ws = _workspace(ws_bytes, dev)
+        ws = scratch.get('fused', ws_bytes, dev, floor=32 << 20)
         stream = ops._stream_handle()
         f32 = dict(dtype=torch.float32, device=dev)
         sums5 = torch.empty(5, n, c, **f32)
@@ -910,7 +900,7 @@ class _DwBnSe(torch.autograd.Function):
             nbytes = ctypes.c_size_t()
             check(lib.stp3_dwconv2d_bwd_weight_workspace(ctypes.byref(dwd), ctypes.byref(nbytes)),
                   'stp3_dwconv2d_bwd_weight_workspace')
-            ws2 = _workspace(max(nbytes.value, ws_bytes), dev)
+            ws2 = scratch.get('fused', max(nbytes.value, ws_bytes), dev, floor=32 << 20)
             # (in the parameter's own layout: autograd takes the tensor as the gradient as it is -- the tap-major form needed a
             # transposing copy per layer and step)
             dwg = torch.empty(wshape, dtype=torch.float32, device=dev)

@@ -5,19 +5,8 @@ import ctypes
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, scratch
 from ._lib import check
-
-_WS = {}
-
-
-def _workspace(nbytes, device):
-    key = ops._ws_key(device)                 # per device and stream (ops._ws_key)
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
-        _WS[key] = ws
-    return ws
 
 
 def supported(x):
@@ -76,7 +65,7 @@ class _CeTopK(torch.autograd.Function):
         lib = _lib.lib()
         need = ctypes.c_size_t()
         check(lib.stp3_ce_topk_workspace_bytes(ctypes.byref(dims), ctypes.byref(need)), 'stp3_ce_topk_workspace_bytes')
-        ws = _workspace(need.value, dev)
+        ws = scratch.get('loss', need.value, dev, floor=1 << 16)
         loss_px = torch.empty(rows, p, dtype=torch.float32, device=dev)
         sel = torch.empty(rows, 2, dtype=torch.float32, device=dev)
         out = torch.empty(1, dtype=torch.float32, device=dev)
@@ -126,7 +115,7 @@ class _RegLoss(torch.autograd.Function):
         lib = _lib.lib()
         need = ctypes.c_size_t()
         check(lib.stp3_reg_loss_workspace_bytes(ctypes.byref(need)), 'stp3_reg_loss_workspace_bytes')
-        ws = _workspace(need.value, dev)
+        ws = scratch.get('loss', need.value, dev, floor=1 << 16)
         out = torch.empty(2, dtype=torch.float32, device=dev)
         check(lib.stp3_reg_loss_fwd(rows, c, h * w, int(norm), float(ignore_value), _dtype_code(x), x.data_ptr(), t.data_ptr(),
                                     ops._opt_ptr(rs), out.data_ptr(), ws.data_ptr(), need.value, ops._stream_handle()),

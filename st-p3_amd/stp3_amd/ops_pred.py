@@ -6,20 +6,10 @@ import weakref
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, scratch
 from ._lib import check
 
 ACT_NONE, ACT_GELU = _lib.ACT_NONE, _lib.ACT_GELU
-_WS = {}
-
-
-def _workspace(nbytes, device):
-    key = ops._ws_key(device)
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-        _WS[key] = ws
-    return ws
 
 
 def layer_norm_supported(x, channels):
@@ -83,7 +73,7 @@ class _LayerNormChannels(torch.autograd.Function):
         nbytes = ctypes.c_size_t()
         lib = _lib.lib()
         check(lib.stp3_layernorm_bwd_workspace(ctypes.byref(dims), ctypes.byref(nbytes)), 'stp3_layernorm_bwd_workspace')
-        ws = _workspace(nbytes.value, x.device)
+        ws = scratch.get('layernorm', nbytes.value, x.device, floor=1 << 20)
         need_w = weight is not None and ctx.needs_input_grad[1]
         need_b = bias is not None and ctx.needs_input_grad[2]
         dg = torch.empty(c, dtype=torch.float32, device=x.device) if need_w else None
