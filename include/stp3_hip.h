@@ -1304,6 +1304,49 @@ typedef struct stp3_vis_desc {
 int stp3_vis_workspace_bytes(const stp3_vis_desc* desc, size_t* bytes);
 int stp3_vis_render(const stp3_vis_desc* desc, uint8_t* video, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * CARLA: recorded samples and simulator ticks from decoded bytes to tensors (csrc/stp3_carla.hip; stp3_amd.carla.CarlaDecoder).
+ * One launch per call for all n images; every entry is re-entrant, only enqueues on `stream`, allocates nothing and does not
+ * synchronise (it can be captured into a graph).  "The window" of an H x W image and a side c <= min(H, W) is rows
+ * H / 2 - c / 2 .. + c and columns W / 2 - c / 2 .. + c (integer divisions): scale_and_crop_image at scale 1,
+ * stp3/datas/CarlaData.py:454-464.
+ *
+ * stp3_carla_frames   camera images: scale_and_crop_image(..., scale=1, crop) + normalise_image, CarlaData.py:377-384,454-464 and
+ *                     carla_agent.py:326-329,370-426.  frames [n][Hs][Ws][Cs] uint8, Cs = 3 | 4; bgr = 1 reverses the first three
+ *                     channels (cv2.cvtColor(x[:, :, :3], COLOR_BGR2RGB)); a fourth channel is ignored.  out [n][3][crop][crop]
+ *                     STP3_DTYPE_F32: (float32(x) / 255 - mean[ch]) / std[ch], two true divisions, bit-equal to the torch
+ *                     statements; STP3_DTYPE_BF16: their rounding to nearest even.
+ * stp3_carla_depth    the 24-bit depth images: get_depth on the window, CarlaData.py:345-353,387-396.  frames [n][Hs][Ws][3] uint8
+ *                     (R, G, B); v = double(R 65536 + G 256 + B) / 16777215.0 * 1000.0 in float64, in that order.  out_kind
+ *                     STP3_DEPTH_OUT_F64 / _F32: the metre map [n][crop][crop] (float32: the rounding of v); STP3_DEPTH_OUT_LABELS:
+ *                     the class ids of stp3/trainer.py:269-276, [n][ceil(crop / downsample)]^2 int64 =
+ *                     (int64)(min(max(v, d_lo), d_hi) - d_lo) in float64 at every downsample-th row and column of the window
+ *                     (d_hi: D_BOUND[1] - 1); only those pixels are decoded.
+ * stp3_carla_hdmap    get_hdmap at scale 1, CarlaData.py:240-260.  frames [n][Hm][Wm][3] uint8; out [n][2][crop][crop]: channel 0
+ *                     lane = pixel == (255, 0, 255), channel 1 drivable = pixel == (54, 52, 46) | lane, both flipped along both
+ *                     axes.
+ * stp3_carla_topdown  get_labels, CarlaData.py:262-280.  frames [n][Ht][Wt] uint8 class ids; Pillow's NEAREST resize to Hr x Wr
+ *                     enters as row_src [Hr] / col_src [Wr] int32 ON THE DEVICE (source row / column of every resized row /
+ *                     column; an entry outside the source is clamped); the window is taken of the resized image.  vehicle,
+ *                     pedestrian [n][1][crop][crop]: pixel == 10 with window rows 89..111 x columns 96..104 (the ego vehicle)
+ *                     cleared, pixel == 4; both flipped along both axes.
+ * Maps (hdmap, topdown) are written as 0 / 1 in float32, float64 or int64 (STP3_CARLA_OUT_*).
+ * STP3_EINVAL: a null pointer, n or a size < 1, a window larger than its image, Cs not 3 | 4, an unknown out_kind, labels with
+ * downsample < 1 or d_lo > d_hi;  STP3_EUNSUP: n > 65 535, crop > 32 768, an image of 2^31 pixels, another out_dtype. */
+#define STP3_CARLA_OUT_F32 0
+#define STP3_CARLA_OUT_F64 1
+#define STP3_CARLA_OUT_I64 2
+
+int stp3_carla_frames(int32_t n, int32_t Hs, int32_t Ws, int32_t Cs, int32_t crop, int32_t bgr, const float* mean,
+                      const float* std, int32_t out_dtype, const uint8_t* frames, void* out, void* stream);
+int stp3_carla_depth(int32_t n, int32_t Hs, int32_t Ws, int32_t crop, int32_t out_kind, int32_t downsample, double d_lo,
+                     double d_hi, const uint8_t* frames, void* out, void* stream);
+int stp3_carla_hdmap(int32_t n, int32_t Hm, int32_t Wm, int32_t crop, int32_t out_kind, const uint8_t* frames, void* out,
+                     void* stream);
+int stp3_carla_topdown(int32_t n, int32_t Ht, int32_t Wt, int32_t Hr, int32_t Wr, int32_t crop, const int32_t* row_src,
+                       const int32_t* col_src, int32_t out_kind, const uint8_t* frames, void* vehicle, void* pedestrian,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -223,6 +223,7 @@ DTYPE_BF16 = 1
 VIS_DTYPE_I64 = 2
 VIS_INSTANCE, VIS_FLOW, VIS_PEDESTRIAN, VIS_PLAN_LABELS, VIS_PLAN_PRED = 1, 2, 4, 8, 16
 DEPTH_OUT_F32, DEPTH_OUT_F64, DEPTH_OUT_LABELS = 0, 1, 2
+CARLA_OUT_F32, CARLA_OUT_F64, CARLA_OUT_I64 = 0, 1, 2
 
 WINDOW_JOBS_MAX = 4
 VOX_REFERENCE = 0
@@ -378,6 +379,10 @@ SIGNATURES = {
     'stp3_window_push': (c_int, [c_int32] * 5 + [ctypes.POINTER(WindowJob), c_void_p]),
     'stp3_vis_workspace_bytes': (c_int, [ctypes.POINTER(VisDesc), ctypes.POINTER(c_size_t)]),
     'stp3_vis_render': (c_int, [ctypes.POINTER(VisDesc), c_void_p, c_void_p, c_void_p]),
+    'stp3_carla_frames': (c_int, [c_int32] * 6 + [ctypes.POINTER(ctypes.c_float)] * 2 + [c_int32] + [c_void_p] * 3),
+    'stp3_carla_depth': (c_int, [c_int32] * 6 + [c_double] * 2 + [c_void_p] * 3),
+    'stp3_carla_hdmap': (c_int, [c_int32] * 5 + [c_void_p] * 3),
+    'stp3_carla_topdown': (c_int, [c_int32] * 6 + [c_void_p] * 2 + [c_int32] + [c_void_p] * 4),
 }
 
 _lib = None

@@ -1637,20 +1637,34 @@ class _WeightShadows:
             block += (r['dims'][0] * r['dims'][1] * r['dims'][2] * r['dims'][3] + 255) // 256
         return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8), block
 
+    def _hold(self):
+        """Strong references to the parameters of every entry, the entries whose parameters are gone dropped first.  The caller
+        keeps the result for as long as it walks ``self.order``: the entries hold weak references only, and a garbage collection
+        -- any allocation inside the walk can start one -- may free a model whose last references were cyclic, after a liveness
+        check made before the walk."""
+        held = [_shadow_params(e) for e in self.order]
+        if any(p is None for p in held):
+            self.order = [e for e, p in zip(self.order, held) if p is not None]
+            self.entries = {id(e['ref']()): e for e in self.order if 'ref' in e}
+            self.assembled = {e['key']: e for e in self.order if e.get('kind') == 'assembled'}
+            held = [p for p in held if p is not None]
+        return held
+
     def _build_table(self):
+        held = self._hold()
         rows = [r for e in self.order for r in self._rows(e)]
         host, self.total_blocks = self._fill_table(rows)
         self.table = host.to(self.device)
         self.rows = len(rows)
+        del held
 
     def refresh(self):
         """Rewrite every shadow from its fp32 master: one launch."""
         if not self.order:
             return
-        if not all(_shadow_alive(e) for e in self.order):
-            self.order = [e for e in self.order if _shadow_alive(e)]
-            self.entries = {id(e['ref']()): e for e in self.order if 'ref' in e}
-            self.assembled = {e['key']: e for e in self.order if e.get('kind') == 'assembled'}
+        n = len(self.order)
+        held = self._hold()                                # (kept to the end of the call: the loop below reads the parameters)
+        if len(self.order) != n:
             if not self.order:
                 return
             self._build_table()
@@ -1666,6 +1680,7 @@ class _WeightShadows:
             else:
                 e['versions'] = tuple(pc['param']()._version for pc in e['pieces'])
             e.pop('phases', None)                  # sub-kernels cut from the flipped shadow (_strided_dgrad)
+        del held
 
     # -- the gradients of the assembled weights: back to their parameters ---------------------------------------------------
     def scatter_rows(self, e):
@@ -1695,11 +1710,17 @@ class _WeightShadows:
                   'stp3_conv2d_scatter_weight_grads')
 
 
-def _shadow_alive(e):
+def _shadow_params(e):
+    """The parameters of an entry (strong references) if all of them still live at the address the entry recorded, else None."""
     if 'ref' in e:
-        w = e['ref']()
-        return w is not None and w.data_ptr() == e['ptr']
-    return all(pc['param']() is not None and pc['param']().data_ptr() == pc['ptr'] for pc in e['pieces'])
+        params, ptrs = [e['ref']()], [e['ptr']]
+    else:
+        params, ptrs = [pc['param']() for pc in e['pieces']], [pc['ptr'] for pc in e['pieces']]
+    return params if all(w is not None and w.data_ptr() == p for w, p in zip(params, ptrs)) else None
+
+
+def _shadow_alive(e):
+    return _shadow_params(e) is not None
 
 
 def _pieces_signature(shape, pieces):
