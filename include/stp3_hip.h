@@ -1049,6 +1049,54 @@ int stp3_image_prep_lds_bytes(const stp3_image_dims* dims, int32_t strip_rows, s
 int stp3_image_prep(const stp3_image_dims* dims, const uint8_t* images, const int32_t* kk_h, const int32_t* bounds_h,
                     const int32_t* kk_v, const int32_t* bounds_v, int32_t strip_rows, void* out, void* stream);
 
+/* Camera images with a PER-IMAGE augmentation (csrc/stp3_image.hip): the Lift-Splat step the reference carries as
+ * img_transform, stp3/utils/tools.py:122-146 -- resize, crop, horizontal flip, in-plane rotation -- with the loader's
+ * resize filter (resize_and_crop_image, stp3/utils/geometry.py:9-13: BILINEAR) and ToTensor + Normalize behind it:
+ *     Image.resize(resize_dims_i, BILINEAR) -> .crop(crop_i) -> [.transpose(FLIP_LEFT_RIGHT)] -> .rotate(rotate_i)
+ * byte-exact with Pillow for all N images of a call.  All crops of a call have the size Wo x Ho.
+ *   images   [N][H][W][3] uint8
+ *   table    [N] stp3_augment_image IN DEVICE MEMORY (a captured graph is replayed with new parameters by rewriting it):
+ *            resize_dims (Wr, Hr), the crop origin (left, top) in the resized image, flip, the six 16.16 fixed-point
+ *            integers of Pillow's Image.rotate (NEAREST, no expand, centre (Wo / 2, Ho / 2), zero fill; the host computes
+ *            them in float64 as Pillow does, stp3_amd.datas.pil_rotate_fixed; 65536, 0, 32768, 0, 65536, 32768 is the
+ *            identity), and where the image's coefficient tables start in `coef`, in int32 elements.
+ *   coef     [coef_len] int32 in device memory: per distinct (source size, resized size) of an axis the table
+ *            kk [resized][ksize] followed anywhere by bounds [resized][2] of stp3_image_prep, every kk row padded with
+ *            zeros to the call's largest tap count `ksize` (one value for both axes).
+ *   strip_rows  as for stp3_image_prep, the largest over the images of the call.
+ *   cols     the LDS strip and coefficient rows hold only the window columns that lie inside the resized image (a contiguous
+ *            range, mirrored by the flip): the largest count over the images of the call (Wo always fits).
+ *   rotate   0: no image of the call is rotated; the rotation integers are not read, `workspace` may be NULL and the call is
+ *            ONE launch.  1: TWO launches -- the resampler writes the images whose rotation is not the identity as cropped
+ *            and flipped bytes [N][Ho][Wo][3] into `workspace` (the others directly into `out`), and a nearest gather
+ *            reads them at Pillow's slanted integer addresses and normalises.
+ *   out      [N][3][Ho][Wo] float32 or bf16.
+ * The kernels clamp every address a table entry produces (rows to the source, table offsets to coef_len, strip rows to
+ * strip_rows): an image whose entry is malformed is left unwritten, it cannot make the kernels read or write outside the
+ * buffers.  Enqueues on `stream` only, allocates nothing, does not synchronise (capturable).
+ * STP3_EINVAL: a null pointer, a size < 1, Wo or Ho above 8192 (Pillow's 32-bit accumulation is not reproduced past it),
+ * rotate with a workspace smaller than stp3_image_augment_workspace_bytes;  STP3_EUNSUP: another out_dtype, N > 65 535,
+ * more LDS than a workgroup has. */
+typedef struct stp3_augment_image {
+    int32_t Wr, Hr;               /* resize_dims of this image */
+    int32_t left, top;            /* crop origin in the resized image */
+    int32_t flip;                 /* 0 | 1 */
+    int32_t rot[6];               /* a0 a1 a2 a3 a4 a5: xin = (a2 + x a0 + y a1) >> 16, yin = (a5 + x a3 + y a4) >> 16 */
+    int32_t kk_h, bounds_h, kk_v, bounds_v;     /* offsets into coef */
+    int32_t reserved;
+} stp3_augment_image;
+typedef struct stp3_augment_dims {
+    int32_t N, H, W;              /* source */
+    int32_t Wo, Ho;               /* crop size, the same for every image */
+    int32_t cols;                 /* 1 .. Wo: the most window columns of one image that lie inside its resized image */
+    int32_t ksize, strip_rows, rotate, coef_len;
+    int32_t out_dtype;            /* STP3_DTYPE_F32 | STP3_DTYPE_BF16 */
+    float mean[3], std[3];
+} stp3_augment_dims;
+int stp3_image_augment_workspace_bytes(const stp3_augment_dims* dims, size_t* bytes);
+int stp3_image_augment(const stp3_augment_dims* dims, const uint8_t* images, const stp3_augment_image* table,
+                       const int32_t* coef, void* workspace, size_t workspace_bytes, void* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Stand-alone voxel summing (csrc/stp3_voxsum.hip): the operator-level twin of the reference's
  * VoxelsSumming.forward / .backward (stp3/utils/geometry.py:302-318 / :320-330) for callers that hold the

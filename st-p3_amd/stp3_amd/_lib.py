@@ -152,6 +152,18 @@ class ImageDims(ctypes.Structure):
                                                'out_dtype')] + [('mean', ctypes.c_float * 3), ('std', ctypes.c_float * 3)])
 
 
+class AugmentImage(ctypes.Structure):
+    """struct stp3_augment_image (include/stp3_hip.h): 16 int32."""
+    _fields_ = ([(k, ctypes.c_int32) for k in ('Wr', 'Hr', 'left', 'top', 'flip')] + [('rot', ctypes.c_int32 * 6)] +
+                [(k, ctypes.c_int32) for k in ('kk_h', 'bounds_h', 'kk_v', 'bounds_v', 'reserved')])
+
+
+class AugmentDims(ctypes.Structure):
+    """struct stp3_augment_dims (include/stp3_hip.h)."""
+    _fields_ = ([(k, ctypes.c_int32) for k in ('N', 'H', 'W', 'Wo', 'Ho', 'cols', 'ksize', 'strip_rows', 'rotate', 'coef_len',
+                                               'out_dtype')] + [('mean', ctypes.c_float * 3), ('std', ctypes.c_float * 3)])
+
+
 class Poly(ctypes.Structure):
     """struct stp3_poly (include/stp3_hip.h)."""
     _fields_ = [('map', ctypes.c_int32), ('nv', ctypes.c_int32), ('value', ctypes.c_float), ('reserved', ctypes.c_int32),
@@ -355,6 +367,8 @@ SIGNATURES = {
     'stp3_image_prep_rows_per_workgroup': (c_int, []),
     'stp3_image_prep_lds_bytes': (c_int, [ctypes.POINTER(ImageDims), c_int32, ctypes.POINTER(c_size_t)]),
     'stp3_image_prep': (c_int, [ctypes.POINTER(ImageDims)] + [c_void_p] * 5 + [c_int32, c_void_p, c_void_p]),
+    'stp3_image_augment_workspace_bytes': (c_int, [ctypes.POINTER(AugmentDims), ctypes.POINTER(c_size_t)]),
+    'stp3_image_augment': (c_int, [ctypes.POINTER(AugmentDims)] + [c_void_p] * 4 + [c_size_t, c_void_p, c_void_p]),
     'stp3_fill_polygons': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     'stp3_instance_labels_workspace_bytes': (c_int, [c_int32, c_int32, ctypes.POINTER(c_size_t)]),
     'stp3_instance_labels': (c_int, [c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p,

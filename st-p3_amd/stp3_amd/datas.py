@@ -10,6 +10,10 @@ data access and stay what they are.
 
 CPU tensors take ``resize_bilinear_pil`` / ``ImagePreprocessor.reference`` below -- the same integer arithmetic written
 with torch operators -- which is what the host-side tests pin against Pillow itself.
+
+``ImageAugmenter`` is the same path with a different resize, crop, horizontal flip and in-plane rotation per image -- the
+Lift-Splat augmentation the reference carries as ``img_transform`` (``stp3/utils/tools.py:115-146``) -- behind
+``stp3_image_augment``, with the matching post-homography for the intrinsics.
 """
 import ctypes
 import math
@@ -176,6 +180,317 @@ class ImagePreprocessor:
         _lib.check(lib.stp3_image_prep(ctypes.byref(d), ops._ptr(flat), ops._ptr(kk_h), ops._ptr(b_h), ops._ptr(kk_v),
                                        ops._ptr(b_v), strip, ops._ptr(out), ops._stream()), 'stp3_image_prep')
         return out.view(*lead, 3, d.Ho, d.Wo)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Per-image augmentation: the Lift-Splat step the reference carries as img_transform (stp3/utils/tools.py:115-146).
+# ----------------------------------------------------------------------------------------------------------------------
+MAX_ROTATE_SIDE = 8192                              # Pillow accumulates the rotation's addresses in 32-bit integers
+
+
+def pil_rotate_fixed(angle, size):
+    """The six 16.16 fixed-point integers ``PIL.Image.rotate(angle)`` (NEAREST, no expand, centre = size / 2) hands to its
+    inner loop, computed in float64 as Pillow does (Image.rotate: the matrix rounded to 15 decimals and recentred;
+    Geometry.c ``affine_fixed``: FIX(v) = floor(v * 65536 + 0.5), the half-pixel offset folded into a2 and a5).  ``size`` =
+    (width, height).  Source address of output pixel (x, y): ((a2 + x a0 + y a1) >> 16, (a5 + x a3 + y a4) >> 16)."""
+    wo, ho = size
+    r = -math.radians(angle % 360.0)
+    m = [round(math.cos(r), 15), round(math.sin(r), 15), 0.0, round(-math.sin(r), 15), round(math.cos(r), 15), 0.0]
+    cx, cy = wo / 2.0, ho / 2.0
+    m[2] = (m[0] * -cx + m[1] * -cy + m[2]) + cx
+    m[5] = (m[3] * -cx + m[4] * -cy + m[5]) + cy
+    fix = lambda v: int(math.floor(v * 65536.0 + 0.5))                                     # noqa: E731
+    return (fix(m[0]), fix(m[1]), fix(m[2] + m[0] * 0.5 + m[1] * 0.5),
+            fix(m[3]), fix(m[4]), fix(m[5] + m[3] * 0.5 + m[4] * 0.5))
+
+
+ROTATE_IDENTITY = (65536, 0, 32768, 0, 65536, 32768)    # = pil_rotate_fixed(0, any size)
+
+
+def rotate_nearest_pil(window, fixed):
+    """``PIL.Image.rotate`` of a (Ho, Wo, C) byte window from its six integers: nearest gather, zero fill."""
+    ho, wo = window.shape[0], window.shape[1]
+    a0, a1, a2, a3, a4, a5 = (int(v) for v in fixed)
+    y = torch.arange(ho, dtype=torch.int64, device=window.device).view(ho, 1)
+    x = torch.arange(wo, dtype=torch.int64, device=window.device).view(1, wo)
+    xin, yin = (a2 + x * a0 + y * a1) >> 16, (a5 + x * a3 + y * a4) >> 16
+    inside = (xin >= 0) & (xin < wo) & (yin >= 0) & (yin < ho)
+    picked = window[yin.clamp(0, ho - 1), xin.clamp(0, wo - 1)]
+    return torch.where(inside.unsqueeze(-1), picked, torch.zeros_like(picked))
+
+
+def get_rot(h):
+    """tools.py:115-119: numpy float64 cos / sin into a float32 tensor."""
+    return torch.Tensor([[np.cos(h), np.sin(h)], [-np.sin(h), np.cos(h)]])
+
+
+class AugmentPlan:
+    """The device-side description of one ``ImageAugmenter`` call: parameter table, coefficient tables, scratch.  The
+    tensors are static: ``ImageAugmenter.plan(params, like=plan)`` rewrites them in place (a captured graph then replays
+    with the new parameters)."""
+
+    def __init__(self, n, size, cols, ksize, strip_rows, rotate, table, coef, workspace):
+        self.n, self.size, self.cols, self.ksize, self.strip_rows, self.rotate = n, size, cols, ksize, strip_rows, rotate
+        self.table, self.coef, self.workspace = table, coef, workspace
+
+
+class ImageAugmenter:
+    """``img_transform`` of the reference (stp3/utils/tools.py:122-146; the Lift-Splat augmentation) for whole batches,
+    with a different resize, crop, horizontal flip and in-plane rotation PER IMAGE, plus ``normalise_image``:
+
+        Image.resize(resize_dims_i, BILINEAR) -> .crop(crop_i) -> [.transpose(FLIP_LEFT_RIGHT)] -> .rotate(rotate_i)
+        -> ToTensor (/ 255) -> Normalize(mean, std)
+
+    byte for byte.  The resize filter is the loader's (``resize_and_crop_image``, geometry.py:9-13: BILINEAR);
+    ``img_transform`` itself names none and would take Pillow's default.
+
+        aug = ImageAugmenter(cfg, resize_lim=(0.193, 0.225), bot_pct_lim=(0.0, 0.22), rot_lim=(-5.4, 5.4), rand_flip=True)
+        params = aug.sample(n, generator)       # host: one dict per image (resize, resize_dims, crop, flip, rotate)
+        x = aug(images_uint8, params)           # (..., H, W, 3) uint8 -> (..., 3, Ho, Wo) float32 | bf16
+        k = aug.intrinsics(k_raw, params)       # K' = P K with P = [[post_rot, post_tran], [0, 0, 1]]
+
+    GPU tensors run stp3_image_augment (csrc/stp3_image.hip), CPU tensors ``reference`` -- the same integer arithmetic
+    with torch operators.  ``sample(train=False)`` gives the loader's fixed parameters: the call then equals
+    ``ImagePreprocessor(cfg)``.
+
+    The depth labels of LIFT.GT_DEPTH (``DepthLabeller``) are NOT augmented: they follow the fixed resize and crop only,
+    so a training run that uses both keeps ``train=False`` parameters or leaves the depth loss out."""
+
+    def __init__(self, cfg=None, source_hw=None, final_dim=None, resize_lim=None, bot_pct_lim=(0.0, 0.0), rot_lim=(0.0, 0.0),
+                 rand_flip=False, eval_params=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+        if cfg is not None:
+            p = get_resizing_and_cropping_parameters(cfg)
+            source_hw = (cfg.IMAGE.ORIGINAL_HEIGHT, cfg.IMAGE.ORIGINAL_WIDTH)
+            final_dim = tuple(cfg.IMAGE.FINAL_DIM)
+            eval_params = {'resize': p['scale_width'], 'resize_dims': p['resize_dims'], 'crop': p['crop']}
+            if resize_lim is None:
+                resize_lim = (p['scale_width'], p['scale_width'])
+        if source_hw is None or final_dim is None:
+            raise ValueError('ImageAugmenter: a configuration, or source_hw and final_dim')
+        self.source_hw, self.final_dim = (int(source_hw[0]), int(source_hw[1])), (int(final_dim[0]), int(final_dim[1]))
+        self.resize_lim = None if resize_lim is None else tuple(float(v) for v in resize_lim)
+        self.bot_pct_lim, self.rot_lim = tuple(float(v) for v in bot_pct_lim), tuple(float(v) for v in rot_lim)
+        self.rand_flip, self.eval_params = bool(rand_flip), eval_params
+        self.mean, self.std = tuple(mean), tuple(std)
+        self._axes, self._spans = {}, {}
+
+    # ---- parameters ----------------------------------------------------------------------------------------------------
+    @staticmethod
+    def make_params(resize, resize_dims, crop, flip=False, rotate=0.0):
+        return {'resize': float(resize), 'resize_dims': (int(resize_dims[0]), int(resize_dims[1])),
+                'crop': tuple(int(c) for c in crop), 'flip': bool(flip), 'rotate': float(rotate)}
+
+    def sample(self, n, generator=None, train=True):
+        """The parameters of ``n`` images, drawn on the host by the Lift-Splat rule (the reference has no such function):
+        resize ~ U(resize_lim), resize_dims = (int(W resize), int(H resize)); crop_h = int((1 - U(bot_pct_lim)) newH) - Ho,
+        crop_w = int(U(0, 1) max(0, newW - Wo)); flip a fair coin if ``rand_flip``; rotate ~ U(rot_lim) degrees.  Five float64
+        draws per image from ``generator``.  ``train=False``: the loader's fixed resize and crop, no flip, no rotation."""
+        if not train:
+            if self.eval_params is None:
+                raise ValueError('ImageAugmenter.sample(train=False): built without a configuration or eval_params')
+            e = self.eval_params
+            return [self.make_params(e['resize'], e['resize_dims'], e['crop']) for _ in range(n)]
+        if self.resize_lim is None:
+            raise ValueError('ImageAugmenter.sample: resize_lim is not set')
+        (h, w), (ho, wo) = self.source_hw, self.final_dim
+        u = torch.rand(n, 5, dtype=torch.float64, generator=generator).tolist()
+        between = lambda lim, t: lim[0] + (lim[1] - lim[0]) * t                             # noqa: E731
+        out = []
+        for u_resize, u_bot, u_left, u_flip, u_rot in u:
+            resize = between(self.resize_lim, u_resize)
+            new_w, new_h = int(w * resize), int(h * resize)
+            crop_h = int((1.0 - between(self.bot_pct_lim, u_bot)) * new_h) - ho
+            crop_w = int(u_left * max(0, new_w - wo))
+            out.append(self.make_params(resize, (new_w, new_h), (crop_w, crop_h, crop_w + wo, crop_h + ho),
+                                        self.rand_flip and u_flip >= 0.5, between(self.rot_lim, u_rot)))
+        return out
+
+    def _check_params(self, params, n=None):
+        if not len(params) or (n is not None and len(params) != n):
+            raise ValueError(f'ImageAugmenter: {len(params)} parameter sets for {n} images')
+        sizes = {(p['crop'][2] - p['crop'][0], p['crop'][3] - p['crop'][1]) for p in params}
+        if len(sizes) != 1:
+            raise ValueError(f'ImageAugmenter: the crops of one call have one size, got {sorted(sizes)}')
+        wo, ho = next(iter(sizes))
+        if wo < 1 or ho < 1 or any(min(p['resize_dims']) < 1 for p in params):
+            raise ValueError('ImageAugmenter: an empty crop or resized image')
+        if wo > MAX_ROTATE_SIDE or ho > MAX_ROTATE_SIDE:
+            raise ValueError(f'ImageAugmenter: a crop of {wo} x {ho} (at most {MAX_ROTATE_SIDE}: Pillow\'s rotation overflows)')
+        return wo, ho
+
+    def _check_images(self, images):
+        if images.dtype != torch.uint8 or images.dim() < 3 or images.shape[-1] != 3 or \
+                tuple(images.shape[-3:-1]) != self.source_hw:
+            raise ValueError(f'ImageAugmenter: images (..., {self.source_hw[0]}, {self.source_hw[1]}, 3) uint8')
+
+    # ---- the matching homography ---------------------------------------------------------------------------------------
+    def post_homography(self, params):
+        """``post_rot`` (n, 2, 2) and ``post_tran`` (n, 2) of ``img_transform`` (tools.py:133-144) started from identity and
+        zero, with its float32 torch statements: a pixel (u, v) of the source lands at post_rot (u, v) + post_tran."""
+        rots, trans = [], []
+        for p in params:
+            crop = p['crop']
+            post_rot, post_tran = torch.eye(2), torch.zeros(2)
+            post_rot *= p['resize']
+            post_tran -= torch.Tensor(crop[:2])
+            if p['flip']:
+                a = torch.Tensor([[-1, 0], [0, 1]])
+                b = torch.Tensor([crop[2] - crop[0], 0])
+                post_rot = a.matmul(post_rot)
+                post_tran = a.matmul(post_tran) + b
+            a = get_rot(p['rotate'] / 180 * np.pi)
+            b = torch.Tensor([crop[2] - crop[0], crop[3] - crop[1]]) / 2
+            b = a.matmul(-b) + b
+            rots.append(a.matmul(post_rot))
+            trans.append(a.matmul(post_tran) + b)
+        return torch.stack(rots), torch.stack(trans)
+
+    def intrinsics(self, intrinsics, params):
+        """K' = [[post_rot, post_tran], [0, 0, 1]] K for (n, 3, 3) intrinsics (any leading shape with n matrices, or one
+        (3, 3) matrix for all).  Products and sums are separate float32 roundings in the order k = 0, 1, 2: without flip and
+        rotation the result equals ``update_intrinsics`` for the same scale and crop."""
+        rot, tran = self.post_homography(params)
+        n = len(params)
+        p = torch.zeros(n, 3, 3)
+        p[:, :2, :2], p[:, :2, 2], p[:, 2, 2] = rot, tran, 1.0
+        k = intrinsics.to(torch.float32)
+        p = p.to(k.device)
+        if k.dim() > 2:
+            p = p.view(*k.shape[:-2], 3, 3)
+        return p[..., :, 0:1] * k[..., 0:1, :] + p[..., :, 1:2] * k[..., 1:2, :] + p[..., :, 2:3] * k[..., 2:3, :]
+
+    # ---- the torch statements ------------------------------------------------------------------------------------------
+    def reference_bytes(self, images, params):
+        """The augmented byte windows (n, Ho, Wo, 3) of (n, H, W, 3) images: what Pillow's chain produces."""
+        wo, ho = self._check_params(params, images.shape[0])
+        out = torch.zeros(images.shape[0], ho, wo, 3, dtype=torch.uint8, device=images.device)
+        for i, p in enumerate(params):
+            wr, hr = p['resize_dims']
+            left, top, right, bottom = p['crop']
+            small = resize_bilinear_pil(images[i], (wr, hr))
+            y0, y1, x0, x1 = max(top, 0), min(bottom, hr), max(left, 0), min(right, wr)      # PIL pads a crop with zeros
+            if y0 < y1 and x0 < x1:
+                out[i, y0 - top:y1 - top, x0 - left:x1 - left] = small[y0:y1, x0:x1]
+            window = out[i].flip(1) if p['flip'] else out[i]
+            out[i] = rotate_nearest_pil(window, pil_rotate_fixed(p['rotate'], (wo, ho)))
+        return out
+
+    def reference(self, images, params):
+        """The torch statements of the whole chain (CPU tensors; what the tests compare with Pillow)."""
+        self._check_images(images)
+        lead = images.shape[:-3]
+        window = self.reference_bytes(images.reshape(-1, *images.shape[-3:]), params)
+        x = window.movedim(-1, -3).to(torch.float32).div(255)                               # ToTensor
+        mean = torch.tensor(self.mean, dtype=torch.float32, device=x.device).view(3, 1, 1)
+        std = torch.tensor(self.std, dtype=torch.float32, device=x.device).view(3, 1, 1)
+        return ((x - mean) / std).view(*lead, 3, *window.shape[1:3])                        # Normalize
+
+    # ---- the kernel ------------------------------------------------------------------------------------------------------
+    def _axis(self, n_in, n_out):
+        if (n_in, n_out) not in self._axes:
+            self._axes[(n_in, n_out)] = pil_bilinear_coefficients(n_in, n_out)
+        return self._axes[(n_in, n_out)]
+
+    def _span(self, hr, top, ho, rows_per_wg):
+        """The most source rows the vertical taps of one workgroup's window rows span (``ImagePreprocessor._strip_rows``)."""
+        key = (hr, top, ho, rows_per_wg)
+        if key not in self._spans:
+            bounds = self._axis(self.source_hw[0], hr)[1].astype(np.int64)
+            y = top + np.arange(-(-ho // rows_per_wg) * rows_per_wg)
+            ok = (y >= 0) & (y < hr) & (y < top + ho)
+            yc = np.clip(y, 0, hr - 1)
+            lo = np.where(ok, bounds[yc, 0], np.iinfo(np.int64).max).reshape(-1, rows_per_wg).min(axis=1)
+            hi = np.where(ok, bounds[yc, 0] + bounds[yc, 1], 0).reshape(-1, rows_per_wg).max(axis=1)
+            self._spans[key] = int(max(1, (hi - lo).max()))
+        return self._spans[key]
+
+    def host_tables(self, params, rows_per_wg, ksize=0):
+        """(table (n, 16) int32 = stp3_augment_image records, coef int32, ksize, strip_rows, any rotation, cols): the
+        coefficient tables deduplicated by (source size, resized size), their rows padded with zeros to the largest tap count;
+        ``cols``: the most window columns of one image that lie inside its resized image (what the LDS strip holds)."""
+        wo, ho = self._check_params(params)
+        h, w = self.source_hw
+        axes = sorted({(w, p['resize_dims'][0]) for p in params} | {(h, p['resize_dims'][1]) for p in params})
+        ksize = max([ksize] + [self._axis(*a)[0].shape[1] for a in axes])
+        parts, where, at = [], {}, 0
+        for a in axes:
+            kk, bounds = self._axis(*a)
+            padded = np.zeros((kk.shape[0], ksize), dtype=np.int32)
+            padded[:, :kk.shape[1]] = kk
+            where[a] = (at, at + padded.size)
+            parts += [padded.reshape(-1), bounds.reshape(-1)]
+            at += padded.size + bounds.size
+        table = np.zeros((len(params), 16), dtype=np.int32)
+        strip_rows, rotate, cols = 1, False, 1
+        for i, p in enumerate(params):
+            wr, hr = p['resize_dims']
+            left = p['crop'][0]
+            first, end = (left + wo - wr, left + wo) if p['flip'] else (-left, wr - left)
+            cols = max(cols, min(wo, end) - max(0, first))
+            fixed = pil_rotate_fixed(p['rotate'], (wo, ho))
+            rotate = rotate or fixed != ROTATE_IDENTITY
+            table[i] = (wr, hr, p['crop'][0], p['crop'][1], int(p['flip'])) + fixed + where[(w, wr)] + where[(h, hr)] + (0,)
+            strip_rows = max(strip_rows, self._span(hr, p['crop'][1], ho, rows_per_wg))
+        return table, np.concatenate(parts).astype(np.int32), ksize, strip_rows, rotate, cols
+
+    def plan(self, params, device, like=None, ksize=0, strip_rows=0, coef_len=0, rotate=None, cols=0):
+        """The ``AugmentPlan`` of ``params`` on ``device``.  ``ksize`` / ``strip_rows`` / ``coef_len`` / ``rotate`` / ``cols`` reserve
+        room for later parameters; ``like``: rewrite that plan's tensors in place instead (it must have the room)."""
+        lib = _lib.lib()
+        rows_per_wg = lib.stp3_image_prep_rows_per_workgroup()
+        if like is not None:
+            ksize = like.ksize
+        table, coef, ksize, span, rot, inside = self.host_tables(params, rows_per_wg, ksize)
+        wo, ho = self._check_params(params)
+        if like is not None:
+            if (len(params), (wo, ho)) != (like.n, like.size) or ksize > like.ksize or span > like.strip_rows or \
+                    coef.size > like.coef.numel() or (rot and not like.rotate) or inside > like.cols:
+                raise ValueError('ImageAugmenter.plan: the parameters do not fit the plan they are to replace')
+            like.table.copy_(torch.from_numpy(table))
+            like.coef[:coef.size].copy_(torch.from_numpy(coef))
+            return like
+        rot = rot if rotate is None else (rot or bool(rotate))
+        buf = np.zeros(max(coef.size, coef_len), dtype=np.int32)
+        buf[:coef.size] = coef
+        workspace = torch.empty(len(params) * ho * wo * 3 if rot else 0, dtype=torch.uint8, device=device)
+        return AugmentPlan(len(params), (wo, ho), min(wo, max(inside, cols)), ksize, max(span, strip_rows), int(rot),
+                           torch.from_numpy(table).to(device),
+                           torch.from_numpy(buf).to(device), workspace)
+
+    def run(self, images, plan, out_dtype=torch.float32, out=None):
+        """One call of stp3_image_augment with a prepared plan: enqueues only (capturable)."""
+        self._check_images(images)
+        if out_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError('ImageAugmenter: out_dtype torch.float32 or torch.bfloat16')
+        lead = images.shape[:-3]
+        flat = images.reshape(-1, *images.shape[-3:]).contiguous()
+        wo, ho = plan.size
+        if flat.shape[0] != plan.n:
+            raise ValueError(f'ImageAugmenter: {flat.shape[0]} images for a plan of {plan.n}')
+        d = _lib.AugmentDims()
+        d.N, d.H, d.W, d.Wo, d.Ho, d.cols = plan.n, self.source_hw[0], self.source_hw[1], wo, ho, plan.cols
+        d.ksize, d.strip_rows, d.rotate, d.coef_len = plan.ksize, plan.strip_rows, plan.rotate, plan.coef.numel()
+        d.out_dtype = _lib.DTYPE_BF16 if out_dtype == torch.bfloat16 else _lib.DTYPE_F32
+        for c in range(3):
+            d.mean[c], d.std[c] = self.mean[c], self.std[c]
+        if out is None:
+            out = torch.empty(plan.n, 3, ho, wo, dtype=out_dtype, device=flat.device)
+        elif out.dtype != out_dtype or out.numel() != plan.n * 3 * ho * wo or not out.is_contiguous():
+            raise ValueError('ImageAugmenter: out does not match the plan')
+        _lib.check(_lib.lib().stp3_image_augment(ctypes.byref(d), ops._ptr(flat), ops._ptr(plan.table), ops._ptr(plan.coef),
+                                                 ops._ptr(plan.workspace) if plan.rotate else None, plan.workspace.numel(),
+                                                 ops._ptr(out), ops._stream()), 'stp3_image_augment')
+        return out.view(*lead, 3, ho, wo)
+
+    def __call__(self, images, params, out_dtype=torch.float32):
+        self._check_images(images)
+        if out_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError('ImageAugmenter: out_dtype torch.float32 or torch.bfloat16')
+        n = images.numel() // (self.source_hw[0] * self.source_hw[1] * 3)
+        self._check_params(params, n)
+        if not images.is_cuda:
+            return self.reference(images, params).to(out_dtype)
+        return self.run(images, self.plan(params, images.device), out_dtype)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
