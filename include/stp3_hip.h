@@ -1292,6 +1292,61 @@ int stp3_depth_labels_from_lidar(const stp3_depth_dims* dims, const float* point
 int stp3_depth_from_maps(const stp3_depth_dims* dims, const void* maps, int32_t map_dtype, void* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Depth labels under the per-image augmentation of the camera images (csrc/stp3_depth_augment.hip): batch['depths'] for the
+ * parameter sets of stp3_image_augment -- a resize, crop, flip and in-plane rotation PER IMAGE.  The composition is this
+ * project's (the reference never combines img_transform with its depth branch); every step is the reference's statement:
+ *   (a), (b) projection and scatter as stp3_depth_from_lidar (stp3/datas/NuscenesData.py:291-293), LiDAR route only;
+ *   (c) F.interpolate over the whole map in the map's dtype, per image: :295 (recompute_scale_factor=True: taps from
+ *       n_src / n_out) for the LiDAR route, :262 (taps from 1 / resize) for stored maps; torch.round, :299 / :266;
+ *   (e) stp3/utils/tools.py:127-130 on the rounded map: .crop (zero fill outside the resized map, negative origins allowed),
+ *       .transpose(FLIP_LEFT_RIGHT), .rotate (NEAREST, no expand, zero fill, Pillow's six 16.16 fixed-point integers);
+ *   (d) class ids of window rows and columns 0, stride, 2 stride, ...: stp3/trainer.py:269-276.
+ * Every per-image quantity is read from device memory (nothing per image is a launch argument), so a captured call replays
+ * with rewritten tables.  Per axis the host lists, image after image, one ENTRY per window row / column in the order the
+ * rotation addresses them (columns after the flip); entry k of an image stands for window coordinate k (separable = 0) or
+ * k stride (separable = 1: no image rotates, so only the label rows and columns are listed):
+ *   tap      [entries][2] int32    the image's slots of i0 and i1, -1 where the row / column lies outside the resized map
+ *   weight   [entries][2] float64  1 - lambda, lambda (for float32 maps: the float32 values, held in doubles)
+ *   slot_src [slots] int32         per image an ASCENDING list of the source indices that are taps
+ *   records  [F N][16] int32       0-5 the rotation's integers a0 .. a5 (source of window pixel (x, y):
+ *                                  ((a2 + x a0 + y a1) >> 16, (a5 + x a3 + y a4) >> 16)); 6, 7 first entry of the image's rows /
+ *                                  columns; 8, 9 first element of its slot lists (y, x); 10, 11 their lengths; 12-15 zero
+ * n = Ho (Wo), or ceil(Ho / stride) (ceil(Wo / stride)) when separable, entries of an image per axis; its winner table is
+ * 2 n_y x 2 n_x words whatever its lists hold.  A record or a table entry that points outside its arrays makes the image's
+ * pixels zero and its points skipped (checked on the device); it never reaches memory outside the buffers.
+ * Output [F][N][ceil(Ho / stride)][ceil(Wo / stride)] of out_kind (STP3_DEPTH_OUT_*); stride > 1 samples the window.
+ *
+ * stp3_augment_depth_from_lidar  (a) - (e) [- (d)]: clear, scatter (slot of a pixel by binary search in the image's lists,
+ *                                integer atomic max), output.  Workspace (stp3_augment_depth_workspace_bytes): the winner
+ *                                tables and 4 bytes per point and camera.
+ * stp3_augment_depth_from_maps   (c) - (e) [- (d)] of stored dense maps [F][N][H][W], float64 or float32 (map_dtype:
+ *                                STP3_DEPTH_OUT_F32 | _F64), arithmetic in the map's dtype: one kernel
+ * Both only enqueue kernels on `stream`, allocate nothing and are deterministic (no floating-point atomics). */
+typedef struct stp3_augment_depth_axis {
+    const int32_t* tap;
+    const double* weight;
+    const int32_t* slot_src;
+    int32_t entries, slots;              /* room of tap / weight (in entries) and of slot_src */
+} stp3_augment_depth_axis;
+
+typedef struct stp3_augment_depth_dims {
+    int32_t F, N, n_total, out_kind;
+    float d_lo, d_hi;
+    int32_t H, W;                        /* source map */
+    int32_t Ho, Wo;                      /* crop window: at most 8192 a side (Pillow's rotation) */
+    int32_t stride, separable;
+    const int32_t* records;
+    stp3_augment_depth_axis y, x;
+} stp3_augment_depth_dims;
+
+int stp3_augment_depth_workspace_bytes(const stp3_augment_depth_dims* dims, size_t* bytes);
+int stp3_augment_depth_from_lidar(const stp3_augment_depth_dims* dims, const float* points, const int32_t* offsets,
+                                  const double* steps, int32_t before, const double* intrinsics, void* workspace,
+                                  size_t workspace_bytes, void* out, void* stream);
+int stp3_augment_depth_from_maps(const stp3_augment_depth_dims* dims, const void* maps, int32_t map_dtype, void* out,
+                                 void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The training video (csrc/stp3_vis.hip): stp3/utils/visualisation.py:208-322 (visualise_output) of ONE sample, painted on the
  * device.  video [T][3][7 H][2 W] uint8, planar; rows of panels top to bottom: instance, future flow, segmentation,
  * centerness, offset, pedestrian, planning; left column labels, right column predictions.  Every panel shows cell

@@ -182,6 +182,20 @@ class DepthDims(ctypes.Structure):
                 [('d_lo', ctypes.c_float), ('d_hi', ctypes.c_float), ('y', DepthAxis), ('x', DepthAxis)])
 
 
+class AugmentDepthAxis(ctypes.Structure):
+    """struct stp3_augment_depth_axis (include/stp3_hip.h)."""
+    _fields_ = ([(k, ctypes.c_void_p) for k in ('tap', 'weight', 'slot_src')] +
+                [(k, ctypes.c_int32) for k in ('entries', 'slots')])
+
+
+class AugmentDepthDims(ctypes.Structure):
+    """struct stp3_augment_depth_dims (include/stp3_hip.h)."""
+    _fields_ = ([(k, ctypes.c_int32) for k in ('F', 'N', 'n_total', 'out_kind')] +
+                [('d_lo', ctypes.c_float), ('d_hi', ctypes.c_float)] +
+                [(k, ctypes.c_int32) for k in ('H', 'W', 'Ho', 'Wo', 'stride', 'separable')] +
+                [('records', ctypes.c_void_p), ('y', AugmentDepthAxis), ('x', AugmentDepthAxis)])
+
+
 class EvalDims(ctypes.Structure):
     """struct stp3_eval_dims (include/stp3_hip.h)."""
     _fields_ = ([(k, ctypes.c_int32) for k in ('B', 'S', 'H', 'W', 'Cs', 'Cp', 'E', 'n_classes', 'first', 'seg_dtype', 'ped_dtype',
@@ -382,6 +396,10 @@ SIGNATURES = {
     'stp3_depth_labels_from_lidar': (c_int, [ctypes.POINTER(DepthDims)] + [c_void_p] * 3 + [c_int32, c_void_p, c_int32,
                                                                                          c_void_p, c_void_p]),
     'stp3_depth_from_maps': (c_int, [ctypes.POINTER(DepthDims), c_void_p, c_int32, c_void_p, c_void_p]),
+    'stp3_augment_depth_workspace_bytes': (c_int, [ctypes.POINTER(AugmentDepthDims), ctypes.POINTER(c_size_t)]),
+    'stp3_augment_depth_from_lidar': (c_int, [ctypes.POINTER(AugmentDepthDims)] + [c_void_p] * 3 + [c_int32] + [c_void_p] * 2 +
+                                      [c_size_t, c_void_p, c_void_p]),
+    'stp3_augment_depth_from_maps': (c_int, [ctypes.POINTER(AugmentDepthDims), c_void_p, c_int32, c_void_p, c_void_p]),
     'stp3_voxels_sum_fwd': (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     'stp3_voxels_sum_bwd': (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     'stp3_bn_eval_coefs': (c_int, [c_void_p, c_int32, ctypes.c_int64, c_void_p]),

@@ -253,8 +253,9 @@ class ImageAugmenter:
     with torch operators.  ``sample(train=False)`` gives the loader's fixed parameters: the call then equals
     ``ImagePreprocessor(cfg)``.
 
-    The depth labels of LIFT.GT_DEPTH (``DepthLabeller``) are NOT augmented: they follow the fixed resize and crop only,
-    so a training run that uses both keeps ``train=False`` parameters or leaves the depth loss out."""
+    The depth labels of LIFT.GT_DEPTH follow the same draw: ``DepthLabeller.from_lidar(..., params=params)`` and
+    ``from_maps(maps, params=params)`` resample, crop, flip and rotate the depth map of every image with its parameter
+    set, so one list drives images, intrinsics and depth labels of a sample."""
 
     def __init__(self, cfg=None, source_hw=None, final_dim=None, resize_lim=None, bot_pct_lim=(0.0, 0.0), rot_lim=(0.0, 0.0),
                  rand_flip=False, eval_params=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
@@ -785,15 +786,18 @@ def assemble_sample(frames, receptive_field, num_instances, planning=None, gt_de
 DEVKIT_BEFORE = (False, False, True, True)          # map_pointcloud_to_image: steps 3 and 4 translate, then rotate
 
 
-def depth_resample_axis(n_src, scale, out_index, dtype=np.float64):
+def depth_resample_axis(n_src, scale, out_index, dtype=np.float64, step=None):
     """Taps and weights of ``F.interpolate(scale_factor=scale, mode='bilinear', align_corners=False)`` along one axis for
     the output indices ``out_index``, as ATen builds them in the map's dtype (UpSampleKernel.cpp: source =
-    max(0, (1 / scale) (o + 0.5) - 0.5), i0 = min(trunc, n - 1), i1 = min(i0 + 1, n - 1), lambda = source - i0 in [0, 1]),
-    and the numbering of the source indices that are taps ("slots", ascending).  Returns a dict of numpy arrays: tap
-    (n_out, 2) int32 slots, weight (n_out, 2) float64 holding the ``dtype`` values, slot_src (n_slot,), src_slot (n_src,)."""
+    max(0, step (o + 0.5) - 0.5), i0 = min(trunc, n - 1), i1 = min(i0 + 1, n - 1), lambda = source - i0 in [0, 1]),
+    and the numbering of the source indices that are taps ("slots", ascending).  The source step is 1 / scale (the scale
+    factor handed on) unless ``step`` names it: with ``recompute_scale_factor=True`` ATen takes n_src / n_out in ``dtype``.
+    Returns a dict of numpy arrays: tap (n_out, 2) int32 slots, weight (n_out, 2) float64 holding the ``dtype`` values,
+    slot_src (n_slot,), src_slot (n_src,)."""
     t = np.dtype(dtype).type
     o = np.asarray(out_index, dtype=np.int64).astype(t)
-    src = np.maximum(t(1.0 / scale) * (o + t(0.5)) - t(0.5), t(0.0))
+    step = t(1.0 / scale) if step is None else t(step)
+    src = np.maximum(step * (o + t(0.5)) - t(0.5), t(0.0))
     i0 = np.minimum(src.astype(np.int64), n_src - 1)
     i1 = np.minimum(i0 + 1, n_src - 1)
     lam = np.clip(src - i0.astype(t), t(0.0), t(1.0))
@@ -816,6 +820,8 @@ class DepthLabeller:
         labels = lab.from_lidar(points, offsets, steps, before, intrinsics, labels=True)    # (a) - (d): (F, N, fH, fW) int64
         depths = lab.from_maps(maps)                                                        # (c) of stored (F, N, H, W) maps
         labels = lab.class_ids(depths)                                                      # (d)
+        depths = lab.from_lidar(..., params=params)     # under ImageAugmenter's per-image parameters: (F, N, Ho, Wo) of the crop
+        depths = lab.from_maps(maps, params=params)     # (csrc/stp3_depth_augment.hip); plan=augment_plan(...)
 
     points (n, 3) float32: the sweeps of the F frames one after the other, offsets (F + 1,) int32 their boundaries;
     steps (F, N, 4, 12) float64: rotation (row-major) and translation of the four rigid steps; before: per step whether it
@@ -1001,13 +1007,18 @@ class DepthLabeller:
         out = self._blend(tab, ay, ax, torch.float64)
         return self._clamp(out.float()) if labels else out.to(out_dtype)
 
-    def reference_from_lidar(self, points, offsets, steps, before, intrinsics, labels=False, out_dtype=torch.float32):
+    def reference_from_lidar(self, points, offsets, steps, before, intrinsics, labels=False, out_dtype=torch.float32,
+                             params=None):
         pixels, depth, keep = self.reference_project(points, offsets, steps, before, intrinsics)
+        if params is not None:
+            return self._reference_augmented(params, pixels.shape[1], labels, out_dtype, (pixels, depth, keep, offsets), None)
         return self.reference_from_pixels(pixels, depth, keep, offsets, labels, out_dtype)
 
-    def reference_from_maps(self, maps, labels=False, out_dtype=torch.float32):
+    def reference_from_maps(self, maps, labels=False, out_dtype=torch.float32, params=None):
         """(c) [+ (d)] of stored maps (F, N, H, W), float64 or float32, in the maps' dtype."""
         self._check_maps(maps)
+        if params is not None:
+            return self._reference_augmented(params, maps.shape[1], labels, out_dtype, None, maps)
         ay, ax = self._tables(labels, np.float64 if maps.dtype == torch.float64 else np.float32, maps.device)
         tab = maps[..., ay['slot_src'].long(), :][..., ax['slot_src'].long()]
         out = self._blend(tab, ay, ax, maps.dtype)
@@ -1068,11 +1079,22 @@ class DepthLabeller:
         return out
 
     def from_lidar(self, points, offsets, steps, before, intrinsics, labels=False, out_dtype=torch.float32, check=False,
-                   fused=False):
+                   fused=False, params=None, plan=None):
         """(a) - (c) [- (d)] from the sweeps.  ``labels=True``: int64 class ids (F, N, fH, fW), equal to
         ``class_ids(from_lidar(...))``, through the winner table of the label rows and columns in global memory like the
         full map (the default: measured faster at the trained shape); with ``fused`` in one launch
-        that keeps the winners of an image in LDS and needs no scratch."""
+        that keeps the winners of an image in LDS and needs no scratch.  ``params`` (F N dictionaries of
+        ``ImageAugmenter.sample`` in (frame, camera) order) or a prepared ``plan`` (``augment_plan``): the labels under the
+        per-image augmentation, (F, N, Ho, Wo) of the parameters' crop size (class ids: every ``downsample``-th row and
+        column of it)."""
+        if params is not None or plan is not None:
+            if fused:
+                raise ValueError('DepthLabeller.from_lidar: the one-launch labels kernel takes no augmentation parameters')
+            if not points.is_cuda:
+                return self.reference_from_lidar(points, offsets, steps, before, intrinsics, labels, out_dtype, params)
+            f, n = self._check_cloud(points, offsets, steps, intrinsics, check)
+            plan = self._plan_for(params, plan, f * n, points.device, labels, None, points.shape[0] * n)
+            return self._run_augmented(plan, f, n, out_dtype, cloud=(points, offsets, steps, before, intrinsics))
         if not points.is_cuda:
             return self.reference_from_lidar(points, offsets, steps, before, intrinsics, labels, out_dtype)
         f, n = self._check_cloud(points, offsets, steps, intrinsics, check)
@@ -1094,11 +1116,16 @@ class DepthLabeller:
                    'stp3_depth_from_lidar')
         return out
 
-    def from_maps(self, maps, labels=False, out_dtype=torch.float32):
-        """(c) [- (d)] of stored dense maps (F, N, H, W), float64 or float32, arithmetic in the maps' dtype."""
+    def from_maps(self, maps, labels=False, out_dtype=torch.float32, params=None, plan=None):
+        """(c) [- (d)] of stored dense maps (F, N, H, W), float64 or float32, arithmetic in the maps' dtype; with ``params``
+        or a ``plan`` under the per-image augmentation, as ``from_lidar``."""
         if not maps.is_cuda:
-            return self.reference_from_maps(maps, labels, out_dtype)
+            return self.reference_from_maps(maps, labels, out_dtype, params)
         self._check_maps(maps)
+        if params is not None or plan is not None:
+            f, n = maps.shape[:2]
+            plan = self._plan_for(params, plan, f * n, maps.device, labels, maps.dtype, 0)
+            return self._run_augmented(plan, f, n, out_dtype, maps=maps)
         dtype, kind = self._out_dtype(labels, out_dtype)
         f, n = maps.shape[:2]
         is64 = maps.dtype == torch.float64
@@ -1108,3 +1135,221 @@ class DepthLabeller:
         _lib.check(_lib.lib().stp3_depth_from_maps(ctypes.byref(d), ops._ptr(maps), _lib.DEPTH_OUT_F64 if is64 else
                                                    _lib.DEPTH_OUT_F32, ops._ptr(out), ops._stream()), 'stp3_depth_from_maps')
         return out
+
+    # ---- under the per-image augmentation of the camera images ------------------------------------
+    def _check_params(self, params, n=None):
+        if params is None or not len(params) or (n is not None and len(params) != n):
+            raise ValueError(f'DepthLabeller: {0 if params is None else len(params)} parameter sets for {n} images')
+        sizes = {(p['crop'][2] - p['crop'][0], p['crop'][3] - p['crop'][1]) for p in params}
+        if len(sizes) != 1:
+            raise ValueError(f'DepthLabeller: the crops of one call have one size, got {sorted(sizes)}')
+        wo, ho = next(iter(sizes))
+        if wo < 1 or ho < 1 or any(min(p['resize_dims']) < 1 for p in params):
+            raise ValueError('DepthLabeller: an empty crop or resized map')
+        if wo > MAX_ROTATE_SIDE or ho > MAX_ROTATE_SIDE:
+            raise ValueError(f'DepthLabeller: a crop of {wo} x {ho} (at most {MAX_ROTATE_SIDE}: Pillow\'s rotation overflows)')
+        h, w = self.source_hw
+        for p in params:
+            want = (int(math.floor(w * p['resize'])), int(math.floor(h * p['resize'])))      # F.interpolate's output size
+            if tuple(p['resize_dims']) != want:
+                raise ValueError(f'DepthLabeller: resize_dims {tuple(p["resize_dims"])} where F.interpolate gives {want}')
+        return wo, ho
+
+    @staticmethod
+    def _source_step(n_src, n_res, maps):
+        """The source step of a route: NuscenesData.py:295 recomputes the scale factor (n_src / n_res), :262 hands 1 / resize on."""
+        return np.float64(n_src) / np.float64(n_res) if maps is None else None
+
+    def _reference_augmented(self, params, n_cam, labels, out_dtype, cloud, maps):
+        """The composition of DESIGN.md section 4.9c in torch operators, image by image: the winners (or the stored map) at
+        the taps of the resized rows and columns inside the crop window, ``_blend`` (which rounds), the zero-padded window,
+        the flip, Pillow's nearest rotation from its fixed-point integers; class ids as ``class_ids`` of that."""
+        h, w = self.source_hw
+        if cloud is not None:
+            pixels, depth, keep, offsets = cloud
+            dev, n_frames, dtype = pixels.device, offsets.numel() - 1, torch.float64
+            bounds = offsets.tolist()
+        else:
+            dev, n_frames, dtype = maps.device, maps.shape[0], maps.dtype
+        wo, ho = self._check_params(params, n_frames * n_cam)
+        np_dtype = np.float64 if dtype == torch.float64 else np.float32
+        out = torch.zeros(n_frames * n_cam, ho, wo, dtype=dtype, device=dev)
+        for i, p in enumerate(params):
+            f, c = divmod(i, n_cam)
+            wr, hr = p['resize_dims']
+            left, top, right, bottom = p['crop']
+            y0, y1, x0, x1 = max(top, 0), min(bottom, hr), max(left, 0), min(right, wr)          # PIL pads a crop with zeros
+            if y0 < y1 and x0 < x1:
+                ay = depth_resample_axis(h, p['resize'], np.arange(y0, y1), np_dtype, self._source_step(h, hr, maps))
+                ax = depth_resample_axis(w, p['resize'], np.arange(x0, x1), np_dtype, self._source_step(w, wr, maps))
+                ay, ax = ({k: torch.from_numpy(v).to(dev) for k, v in t.items()} for t in (ay, ax))
+                if cloud is None:
+                    tab = maps[f, c][ay['slot_src'].long(), :][:, ax['slot_src'].long()]
+                else:
+                    nsy, nsx = ay['slot_src'].numel(), ax['slot_src'].numel()
+                    a, b = max(0, bounds[f]), min(pixels.shape[0], bounds[f + 1])
+                    tab = torch.zeros(nsy, nsx, dtype=dtype, device=dev)
+                    if a < b:
+                        px, py, z = pixels[a:b, c, 0].long(), pixels[a:b, c, 1].long(), depth[a:b, c]
+                        ok = keep[a:b, c] & (px >= 0) & (px < w) & (py >= 0) & (py < h)
+                        sx, sy = ax['src_slot'].long()[px.clamp(0, w - 1)], ay['src_slot'].long()[py.clamp(0, h - 1)]
+                        ok = ok & (sx >= 0) & (sy >= 0)
+                        zero = torch.zeros_like(sx)
+                        local = torch.arange(1, b - a + 1, device=dev)                           # last point in point order wins
+                        win = torch.zeros(nsy * nsx, dtype=torch.int64, device=dev)
+                        win.scatter_reduce_(0, torch.where(ok, sy * nsx + sx, zero), torch.where(ok, local, zero), 'amax')
+                        tab = torch.where(win > 0, z[(win - 1).clamp(min=0)], torch.zeros((), dtype=dtype, device=dev)).view(nsy, nsx)
+                out[i, y0 - top:y1 - top, x0 - left:x1 - left] = self._blend(tab, ay, ax, dtype)
+            window = out[i].flip(1) if p['flip'] else out[i]
+            out[i] = rotate_nearest_pil(window.unsqueeze(-1), pil_rotate_fixed(p['rotate'], (wo, ho))).squeeze(-1)
+        out = out.view(n_frames, n_cam, ho, wo)
+        return self.class_ids(out.float()) if labels else out.to(out_dtype)
+
+    def _augment_layout(self, n, n_y, n_x):
+        """Where the tables lie in a plan's one buffer of int32 words (the weights: float64, at an even word)."""
+        sizes = (('records', 16 * n), ('tap_y', 2 * n * n_y), ('tap_x', 2 * n * n_x), ('slot_y', 2 * n * n_y), ('slot_x', 2 * n * n_x),
+                 ('weight_y', 4 * n * n_y), ('weight_x', 4 * n * n_x))
+        at, out = 0, {}
+        for k, size in sizes:
+            out[k] = (at, at + size)
+            at += size
+        return out, at
+
+    def _augment_host(self, params, separable, maps):
+        """The records and tables of stp3_augment_depth_* (include/stp3_hip.h) for ``params`` as one int32 array: per axis
+        the arithmetic of ``depth_resample_axis`` for all images at once (a batch of 72 images is 144 tables)."""
+        wo, ho = self._check_params(params)
+        h, w = self.source_hw
+        st = self.downsample if separable else 1
+        n, n_y, n_x = len(params), -(-ho // st), -(-wo // st)
+        layout, words = self._augment_layout(n, n_y, n_x)
+        blob = np.zeros(words, dtype=np.int32)
+        part = {k: blob[a:b] for k, (a, b) in layout.items()}
+        records = part['records'].reshape(n, 16)
+        t = np.float32 if maps == torch.float32 else np.float64
+        resize = np.array([p['resize'] for p in params], dtype=np.float64)
+        image = np.arange(n)[:, None]
+        for name, n_src, side, count, at, flips in (('y', h, ho, n_y, 1, None), ('x', w, wo, n_x, 0, [p['flip'] for p in params])):
+            n_res = np.array([p['resize_dims'][at] for p in params], dtype=np.int64)[:, None]
+            origin = np.array([p['crop'][at] for p in params], dtype=np.int64)[:, None]
+            k = (np.arange(count, dtype=np.int64) * st)[None]
+            if flips is not None:
+                k = np.where(np.array(flips, dtype=bool)[:, None], side - 1 - k, k)
+            r = origin + k                                                                   # the resized row / column of an entry
+            valid = (r >= 0) & (r < n_res)
+            step = (1.0 / resize).astype(t) if maps is not None else (np.float64(n_src) / n_res[:, 0].astype(np.float64))
+            src = np.maximum(step[:, None] * (r.astype(t) + t(0.5)) - t(0.5), t(0.0))
+            i0 = np.minimum(src.astype(np.int64), n_src - 1)
+            i1 = np.minimum(i0 + 1, n_src - 1)
+            lam = np.clip(src - i0.astype(t), t(0.0), t(1.0))
+            present = np.zeros((n, n_src), dtype=bool)                                       # the source indices that are taps
+            rows = np.broadcast_to(image, r.shape)[valid]
+            present[rows, i0[valid]] = True
+            present[rows, i1[valid]] = True
+            src_slot = np.cumsum(present, axis=1) - 1
+            n_slot = present.sum(axis=1)
+            first = np.cumsum(n_slot) - n_slot
+            slots = np.nonzero(present)[1]                                                   # image after image, ascending
+            part['slot_' + name][:len(slots)] = slots
+            tap = part['tap_' + name].reshape(n, count, 2)
+            tap[..., 0] = np.where(valid, src_slot[image, i0], -1)
+            tap[..., 1] = np.where(valid, src_slot[image, i1], -1)
+            weight = part['weight_' + name].view(np.float64).reshape(n, count, 2)
+            weight[..., 0] = np.where(valid, t(1.0) - lam, t(0.0))
+            weight[..., 1] = np.where(valid, lam, t(0.0))
+            records[:, 6 + (1 - at)] = np.arange(n) * count
+            records[:, 8 + (1 - at)] = first
+            records[:, 10 + (1 - at)] = n_slot
+        records[:, :6] = [pil_rotate_fixed(p['rotate'], (wo, ho)) for p in params]
+        return blob
+
+    @staticmethod
+    def _rotates(params, size):
+        return any(pil_rotate_fixed(p['rotate'], size) != ROTATE_IDENTITY for p in params)
+
+    def augment_plan(self, params, device, labels=False, like=None, maps=None, points=0, rotate=None):
+        """The ``DepthAugmentPlan`` of ``params`` (F N dictionaries, (frame, camera) order) on ``device``: records, axis tables
+        and the winner-table workspace as static tensors.  ``maps``: None for ``from_lidar``, the maps' dtype for
+        ``from_maps`` (the two reference branches take their taps differently, and a float32 map its weights in float32).
+        ``points``: room for the depths of that many (point, camera) pairs (``from_lidar`` grows it outside a capture).
+        With ``labels`` and no rotating image the tables hold the label rows and columns only; ``rotate=True`` reserves the
+        window's tables for later parameters that rotate.  ``like``: rewrite that plan's tensors in place instead, so that
+        a captured call replays with the new parameters; ValueError if they do not fit the room it reserved."""
+        wo, ho = self._check_params(params)
+        rotates = self._rotates(params, (wo, ho))
+        if like is not None:
+            if (len(params), (wo, ho)) != (like.n, like.size) or (rotates and like.separable):
+                raise ValueError('DepthLabeller.augment_plan: the parameters do not fit the plan they are to replace')
+            like.blob.copy_(torch.from_numpy(self._augment_host(params, like.separable, like.maps)))
+            return like
+        if maps not in (None, torch.float32, torch.float64):
+            raise ValueError('DepthLabeller.augment_plan: maps is None (LiDAR), torch.float64 or torch.float32')
+        separable = bool(labels) and not rotates and not rotate
+        blob = torch.from_numpy(self._augment_host(params, separable, maps)).to(device)
+        st = self.downsample if separable else 1
+        plan = DepthAugmentPlan(len(params), (wo, ho), bool(labels), separable, maps, blob,
+                                self._augment_layout(len(params), -(-ho // st), -(-wo // st))[0])
+        if maps is None:
+            plan.table_bytes = len(params) * 4 * -(-ho // st) * -(-wo // st) * 4
+            plan.workspace = torch.empty(plan.table_bytes + 4 * int(points), dtype=torch.uint8, device=device)
+        return plan
+
+    def _plan_for(self, params, plan, n, device, labels, maps, pairs):
+        if plan is None:
+            self._check_params(params, n)
+            return self.augment_plan(params, device, labels, maps=maps, points=pairs)
+        if plan.n != n or plan.maps != maps or plan.labels != bool(labels) or plan.blob.device != device:
+            raise ValueError('DepthLabeller: the plan was made for other images, another route or another output')
+        if maps is None and plan.workspace.numel() < plan.table_bytes + 4 * pairs:
+            if torch.cuda.is_current_stream_capturing():
+                raise ValueError('DepthLabeller: the plan has no room for this cloud (augment_plan(points=...))')
+            plan.workspace = torch.empty(plan.table_bytes + 4 * pairs, dtype=torch.uint8, device=device)
+        return plan
+
+    def _augment_dims(self, plan, f, n, n_total, kind):
+        wo, ho = plan.size
+        d = _lib.AugmentDepthDims()
+        d.F, d.N, d.n_total, d.out_kind = f, n, n_total, kind
+        d.d_lo, d.d_hi = self.d_bound[0], self.d_bound[1] - 1
+        d.H, d.W, d.Ho, d.Wo = self.source_hw[0], self.source_hw[1], ho, wo
+        d.stride, d.separable = self.downsample if plan.labels else 1, int(plan.separable)
+        d.records = plan.part('records').data_ptr()
+        for axis, name in ((d.y, 'y'), (d.x, 'x')):
+            axis.tap, axis.weight, axis.slot_src = (plan.part(k + name).data_ptr() for k in ('tap_', 'weight_', 'slot_'))
+            axis.entries, axis.slots = plan.part('tap_' + name).numel() // 2, plan.part('slot_' + name).numel()
+        return d
+
+    def _run_augmented(self, plan, f, n, out_dtype, cloud=None, maps=None):
+        """One call of stp3_augment_depth_from_lidar / _from_maps with a prepared plan: enqueues only (capturable)."""
+        dtype, kind = self._out_dtype(plan.labels, out_dtype)
+        wo, ho = plan.size
+        d = self._augment_dims(plan, f, n, 0 if cloud is None else cloud[0].shape[0], kind)
+        out = torch.empty(f, n, -(-ho // d.stride), -(-wo // d.stride), dtype=dtype, device=plan.blob.device)
+        lib = _lib.lib()
+        if cloud is None:
+            maps = maps.contiguous()
+            _lib.check(lib.stp3_augment_depth_from_maps(ctypes.byref(d), ops._ptr(maps), _lib.DEPTH_OUT_F64 if maps.dtype ==
+                                                        torch.float64 else _lib.DEPTH_OUT_F32, ops._ptr(out), ops._stream()),
+                       'stp3_augment_depth_from_maps')
+            return out
+        points, offsets, steps, before, intrinsics = cloud
+        points, offsets, steps, intrinsics = (t.contiguous() for t in (points, offsets, steps, intrinsics))
+        _lib.check(lib.stp3_augment_depth_from_lidar(ctypes.byref(d), ops._ptr(points), ops._ptr(offsets), ops._ptr(steps),
+                                                     self._before_mask(before), ops._ptr(intrinsics), ops._ptr(plan.workspace),
+                                                     plan.workspace.numel(), ops._ptr(out), ops._stream()),
+                   'stp3_augment_depth_from_lidar')
+        return out
+
+
+class DepthAugmentPlan:
+    """The device-side description of one augmented ``DepthLabeller`` call: the per-image records and the axis tables in one
+    static buffer, the winner-table workspace.  ``DepthLabeller.augment_plan(params, like=plan)`` rewrites them in place (a
+    captured graph then replays with the new parameters)."""
+
+    def __init__(self, n, size, labels, separable, maps, blob, layout):
+        self.n, self.size, self.labels, self.separable, self.maps, self.blob, self.layout = n, size, labels, separable, maps, blob, layout
+        self.workspace, self.table_bytes = None, 0
+
+    def part(self, name):
+        a, b = self.layout[name]
+        return self.blob[a:b]
