@@ -1098,6 +1098,59 @@ int stp3_image_augment(const stp3_augment_dims* dims, const uint8_t* images, con
                        const int32_t* coef, void* workspace, size_t workspace_bytes, void* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * JPEG camera frames (csrc/stp3_jpeg_entropy.h, csrc/stp3_jpeg.hip): a baseline decode split where it is serial.  The
+ * Huffman bit stream is decoded on the HOST into quantised coefficients; dequantisation, inverse DCT, chroma up-sampling
+ * and colour conversion run in ONE kernel whose output is the `images` of stp3_image_prep / stp3_image_augment, byte for
+ * byte what Pillow (libjpeg-turbo, default settings) decodes.  Restated from libjpeg's published source: jidctint.c
+ * (jpeg_idct_islow), jdsample.c (h2v1 / h2v2 fancy up-sampling and its replication fall-back for chroma widths <= 2,
+ * reproduced), jdmainct.c (edge context rows), jdcolor.c (ycc_rgb_convert), jdmaster.c (the range-limit table), jdapimin.c
+ * (how the colour space is guessed), jdhuff.c (look-ahead Huffman decoding).
+ *
+ * Host (plain C++, no GPU call; allocates nothing persistent, keeps no state, throws nothing):
+ *   stp3_jpeg_info     parses the markers up to the scan and fills the header, so that the caller can size its buffers.
+ *   stp3_jpeg_entropy  decodes the scan.  coef: header.coef_count int16 (room for coef_capacity ELEMENTS), component after
+ *                      component, each [blocks_y][blocks_x][64] in NATURAL (de-zigzagged, row-major) order, every block of
+ *                      the MCU grid, padding blocks included (blocks_x = mcus_x * h factor, blocks_y = mcus_y * v factor).
+ *                      quant: [3][64] uint16 in natural order, one table per component (grey: three copies).
+ *   Streams: SOF0 / SOF1, 8-bit samples, Huffman, ONE scan; one component (grey; decoded 1x1) or Y Cb Cr with luma
+ *   sampling 1x1, 2x1 or 2x2 and chroma 1x1 (4:4:4, 4:2:2, 4:2:0); restart intervals; 8- and 16-bit quantisation tables;
+ *   sides up to 16 384.  STP3_EUNSUP, decided before anything is written: progressive, arithmetic, lossless, 12-bit, four
+ *   components (CMYK / YCCK), RGB streams (Adobe transform 0, or ids 'R','G','B' without JFIF), other sampling factors, a
+ *   scan that holds only part of the components.  STP3_EINVAL: a null pointer, a malformed or truncated stream (a code no
+ *   table assigns, a run past coefficient 63, a table the scan names but no segment defined, a missing RSTn or EOI, data
+ *   that ends early, a coefficient whose dequantised value |coefficient * quantiser| exceeds 32 767 -- no 8-bit encoder
+ *   writes one, libjpeg-turbo's SIMD IDCT holds 16 bits there, and the byte equality with Pillow is claimed inside that
+ *   bound), a buffer smaller than coef_count.  Bytes that are no marker in front of an RSTn or of EOI are skipped, as
+ *   libjpeg skips them with a warning.  Every read is checked against len, every write against the buffer.
+ *
+ * Device: stp3_jpeg_reconstruct, all N images of a call at once; they share width, height, components and sampling.
+ *   coef   [N][coef_count] int16 in device memory, as stp3_jpeg_entropy wrote them
+ *   quant  [N][3][64] uint16 IN DEVICE MEMORY, per image (a captured graph is replayed on new images by rewriting both)
+ *   out    [N][height][width][3] uint8 RGB (grey: the sample three times, as Image.convert('RGB'))
+ *   A workgroup owns stp3_jpeg_strip_rows(vs) pixel rows of one image (whole MCU rows) and keeps their samples in LDS.
+ * Enqueues on `stream` only, allocates nothing, does not synchronise (capturable).  STP3_EINVAL: a null pointer, a size < 1,
+ * components / sampling outside the list above;  STP3_EUNSUP: N > 65 535, a side above 16 384, a strip wider than LDS (about
+ * 2 500 pixels). */
+typedef struct stp3_jpeg_header {
+    int32_t width, height;
+    int32_t components;           /* 1 | 3 */
+    int32_t hs, vs;               /* luma sampling factors (chroma is 1 x 1) */
+    int32_t mcus_x, mcus_y;
+    int32_t blocks_x[3], blocks_y[3];
+    int32_t restart_interval;     /* MCUs, 0: none */
+    int32_t coef_count;           /* int16 elements of one image */
+} stp3_jpeg_header;
+typedef struct stp3_jpeg_dims {
+    int32_t N, width, height, components, hs, vs;
+} stp3_jpeg_dims;
+int stp3_jpeg_info(const uint8_t* data, size_t len, stp3_jpeg_header* header);
+int stp3_jpeg_entropy(const uint8_t* data, size_t len, int16_t* coef, size_t coef_capacity, uint16_t* quant,
+                      stp3_jpeg_header* header);
+int stp3_jpeg_strip_rows(int32_t vs);
+int stp3_jpeg_reconstruct(const stp3_jpeg_dims* dims, const int16_t* coef, const uint16_t* quant, uint8_t* out,
+                          void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Stand-alone voxel summing (csrc/stp3_voxsum.hip): the operator-level twin of the reference's
  * VoxelsSumming.forward / .backward (stp3/utils/geometry.py:302-318 / :320-330) for callers that hold the
  * rank-sorted row matrix; the fused path above never builds it.

@@ -164,6 +164,18 @@ class AugmentDims(ctypes.Structure):
                                                'out_dtype')] + [('mean', ctypes.c_float * 3), ('std', ctypes.c_float * 3)])
 
 
+class JpegHeader(ctypes.Structure):
+    """struct stp3_jpeg_header (include/stp3_hip.h)."""
+    _fields_ = ([(k, ctypes.c_int32) for k in ('width', 'height', 'components', 'hs', 'vs', 'mcus_x', 'mcus_y')] +
+                [('blocks_x', ctypes.c_int32 * 3), ('blocks_y', ctypes.c_int32 * 3), ('restart_interval', ctypes.c_int32),
+                 ('coef_count', ctypes.c_int32)])
+
+
+class JpegDims(ctypes.Structure):
+    """struct stp3_jpeg_dims (include/stp3_hip.h)."""
+    _fields_ = [(k, ctypes.c_int32) for k in ('N', 'width', 'height', 'components', 'hs', 'vs')]
+
+
 class Poly(ctypes.Structure):
     """struct stp3_poly (include/stp3_hip.h)."""
     _fields_ = [('map', ctypes.c_int32), ('nv', ctypes.c_int32), ('value', ctypes.c_float), ('reserved', ctypes.c_int32),
@@ -383,6 +395,10 @@ SIGNATURES = {
     'stp3_image_prep': (c_int, [ctypes.POINTER(ImageDims)] + [c_void_p] * 5 + [c_int32, c_void_p, c_void_p]),
     'stp3_image_augment_workspace_bytes': (c_int, [ctypes.POINTER(AugmentDims), ctypes.POINTER(c_size_t)]),
     'stp3_image_augment': (c_int, [ctypes.POINTER(AugmentDims)] + [c_void_p] * 4 + [c_size_t, c_void_p, c_void_p]),
+    'stp3_jpeg_info': (c_int, [c_void_p, c_size_t, ctypes.POINTER(JpegHeader)]),
+    'stp3_jpeg_entropy': (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, ctypes.POINTER(JpegHeader)]),
+    'stp3_jpeg_strip_rows': (c_int, [c_int32]),
+    'stp3_jpeg_reconstruct': (c_int, [ctypes.POINTER(JpegDims), c_void_p, c_void_p, c_void_p, c_void_p]),
     'stp3_fill_polygons': (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     'stp3_instance_labels_workspace_bytes': (c_int, [c_int32, c_int32, ctypes.POINTER(c_size_t)]),
     'stp3_instance_labels': (c_int, [c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p,
@@ -449,6 +465,8 @@ def lib():
     _lib = handle
     return _lib
 
+
+STP3_EINVAL, STP3_EUNSUP, STP3_ENOSPACE = -10001, -10002, -10003          # include/stp3_hip.h
 
 _ERRORS = {-10001: 'STP3_EINVAL (bad dimension / null pointer)',
            -10002: 'STP3_EUNSUP (unsupported configuration)',

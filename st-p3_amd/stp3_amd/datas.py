@@ -14,9 +14,17 @@ with torch operators -- which is what the host-side tests pin against Pillow its
 ``ImageAugmenter`` is the same path with a different resize, crop, horizontal flip and in-plane rotation per image -- the
 Lift-Splat augmentation the reference carries as ``img_transform`` (``stp3/utils/tools.py:115-146``) -- behind
 ``stp3_image_augment``, with the matching post-homography for the intrinsics.
+
+``JpegDecoder`` (at the end of the file) moves the boundary into the JPEG decoder: the Huffman bit stream of a baseline file is
+decoded on host threads, the rest of the decode is one kernel (``stp3_jpeg_reconstruct``) whose output, byte for byte Pillow's,
+is what the two classes above read.
 """
+import collections
+import concurrent.futures
 import ctypes
+import io
 import math
+import os
 
 import numpy as np
 import torch
@@ -1353,3 +1361,321 @@ class DepthAugmentPlan:
     def part(self, name):
         a, b = self.layout[name]
         return self.blob[a:b]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# JPEG camera frames: the Huffman half on host threads (csrc/stp3_jpeg_entropy.h), the dense half in one kernel
+# (csrc/stp3_jpeg.hip: stp3_jpeg_reconstruct), byte-exact with Pillow's decode.  Its output is the input of
+# ImagePreprocessor / ImageAugmenter above.
+# ----------------------------------------------------------------------------------------------------------------------
+class JpegUnsupported(ValueError):
+    """A stream the entropy decoder does not take (progressive, CMYK, another sampling, ...) met with ``fallback=False``."""
+
+
+JpegGeometry = collections.namedtuple('JpegGeometry', 'width height components hs vs')
+JpegInfo = collections.namedtuple('JpegInfo', 'width height components hs vs mcus_x mcus_y blocks restart_interval coef_count')
+_SOF_NAMES = {0xC2: 'progressive', 0xC3: 'lossless', 0xC5: 'hierarchical', 0xC6: 'hierarchical progressive', 0xC7: 'hierarchical lossless',
+              0xC9: 'arithmetic coding', 0xCA: 'progressive, arithmetic coding', 0xCB: 'lossless, arithmetic coding',
+              0xCD: 'hierarchical, arithmetic coding', 0xCE: 'hierarchical, arithmetic coding', 0xCF: 'hierarchical, arithmetic coding'}
+
+
+def _geometry(info):
+    return JpegGeometry(info.width, info.height, info.components, info.hs, info.vs)
+
+
+def _coef_count(g):
+    mx, my = -(-g.width // (8 * g.hs)), -(-g.height // (8 * g.vs))
+    return mx * my * (g.hs * g.vs + (2 if g.components == 3 else 0)) * 64
+
+
+def jpeg_unsupported_reason(data):
+    """Why stp3_jpeg_info answered STP3_EUNSUP, in words (the C entry returns the code only): a walk over the markers."""
+    data = bytes(data)
+    pos, frame, jfif, adobe = 2, None, False, None
+    while pos + 4 <= len(data) and data[pos] == 0xFF:
+        m, n = data[pos + 1], (data[pos + 2] << 8) | data[pos + 3]
+        seg = data[pos + 4:pos + 2 + n]
+        if m in _SOF_NAMES:
+            return _SOF_NAMES[m]
+        if m in (0xC0, 0xC1) and len(seg) >= 6:
+            frame = seg
+        jfif = jfif or (m == 0xE0 and seg[:5] == b'JFIF\0')
+        if m == 0xEE and seg[:5] == b'Adobe' and len(seg) >= 12:
+            adobe = seg[11]
+        if m == 0xDA and frame is not None:
+            nc = frame[5]
+            comps = [(frame[6 + 3 * c], frame[7 + 3 * c] >> 4, frame[7 + 3 * c] & 15) for c in range(nc)]
+            if frame[0] != 8:
+                return f'{frame[0]}-bit samples'
+            if nc not in (1, 3):
+                return f'{nc} components' + (' (CMYK / YCCK)' if nc == 4 else '')
+            if max((frame[1] << 8) | frame[2], (frame[3] << 8) | frame[4]) > 16384:
+                return 'a side above 16 384 pixels'
+            if nc == 3 and (comps[0][1:] not in ((1, 1), (2, 1), (2, 2)) or comps[1][1:] != (1, 1) or comps[2][1:] != (1, 1)):
+                return 'sampling factors ' + ', '.join(f'{h}x{v}' for _, h, v in comps)
+            if nc == 3 and not jfif and (adobe == 0 or (adobe is None and bytes(c[0] for c in comps) == b'RGB')):
+                return 'an RGB stream (no YCbCr transform)'
+            if seg and seg[0] != nc:
+                return 'more than one scan'
+            break
+        pos += 2 + n
+    return 'not a stream of the supported kind'
+
+
+class JpegGroup:
+    """The images of a ``JpegBatch`` that share one geometry: where they sit in the call, their coefficients (n, coef_count)
+    int16 and quantisation tables (n, 3, 64) uint16 bits in int16 storage, both in pinned host memory where there is a GPU."""
+
+    def __init__(self, geometry, indices, pin):
+        self.geometry, self.indices = geometry, list(indices)
+        self.coef = torch.empty(len(self.indices), _coef_count(geometry), dtype=torch.int16, pin_memory=pin)
+        self.quant = torch.empty(len(self.indices), 3, 64, dtype=torch.int16, pin_memory=pin)
+
+
+class JpegBatch:
+    """What ``JpegDecoder.entropy`` returns: per geometry a ``JpegGroup``; ``fallback`` maps the index of every stream the
+    entropy decoder does not take to (reason, its bytes) -- Pillow decodes those on the host."""
+
+    def __init__(self, n, groups, fallback, sizes):
+        self.n, self.groups, self.fallback, self.sizes = n, groups, fallback, sizes          # sizes: (height, width) per image
+
+    def layout(self):
+        return [(g.geometry, tuple(g.indices)) for g in self.groups]
+
+
+class JpegDecoder:
+    """JPEG bytes -> (N, H, W, 3) uint8 RGB on the GPU, equal to ``PIL.Image.open(...).convert('RGB')`` byte for byte.
+
+        dec = JpegDecoder()
+        images = dec(list_of_bytes, 'cuda')                  # entropy decode on host threads + one kernel per geometry
+        x = ImagePreprocessor(cfg)(images)                   # or ImageAugmenter(cfg, ...)(images, params)
+
+    ``workers``: host threads of the entropy decode (ctypes releases the GIL), at most ``min(16, os.cpu_count())`` by default.
+    ``fallback``: a stream the entropy decoder answers with STP3_EUNSUP (progressive, CMYK, 4:1:1, ...) is decoded by Pillow on
+    the host and uploaded into the same slot of the result; ``fallback=False`` raises ``JpegUnsupported`` instead.  A corrupt
+    stream (STP3_EINVAL) always raises."""
+
+    def __init__(self, workers=None, fallback=True):
+        self.workers = max(1, int(workers)) if workers is not None else min(16, os.cpu_count() or 1)
+        self.fallback = fallback
+        self._pool = None
+
+    # ---- host ---------------------------------------------------------------------------------------------------------
+    def info(self, data):
+        data = bytes(data)
+        h = _lib.JpegHeader()
+        rc = _lib.lib().stp3_jpeg_info(data, len(data), ctypes.byref(h))
+        if rc == _lib.STP3_EUNSUP:
+            raise JpegUnsupported(jpeg_unsupported_reason(data))
+        _lib.check(rc, 'stp3_jpeg_info')
+        blocks = tuple((h.blocks_y[c], h.blocks_x[c]) for c in range(h.components))
+        return JpegInfo(h.width, h.height, h.components, h.hs, h.vs, h.mcus_x, h.mcus_y, blocks, h.restart_interval, h.coef_count)
+
+    def _map(self, fn, items):
+        if self.workers == 1 or len(items) < 2:
+            return [fn(i) for i in items]
+        if self._pool is None:
+            self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=self.workers)
+        return list(self._pool.map(fn, items))
+
+    def entropy(self, streams, out=None):
+        """Huffman-decode ``streams`` (bytes-like objects) into a ``JpegBatch``; ``out``: a batch of the same layout to refill."""
+        streams = [s if isinstance(s, bytes) else bytes(s) for s in streams]
+        lib = _lib.lib()
+        def header(s):
+            try:
+                return self.info(s)
+            except (JpegUnsupported, _lib.Stp3HipError) as e:
+                return e
+
+        infos, fallback = self._map(header, streams), {}
+        for i, f in enumerate(infos):
+            if isinstance(f, JpegUnsupported):
+                if not self.fallback:
+                    raise JpegUnsupported(f'image {i}: {f}') from None
+                fallback[i] = (str(f), streams[i])
+                infos[i] = None
+            elif isinstance(f, Exception):
+                raise _lib.Stp3HipError(f'image {i}: {f}') from None
+        order = {}
+        for i, f in enumerate(infos):
+            if f is not None:
+                order.setdefault(_geometry(f), []).append(i)
+        layout = [(g, tuple(idx)) for g, idx in order.items()]
+        if out is not None and out.layout() == layout and out.n == len(streams):
+            groups = out.groups
+        else:
+            if out is not None:
+                raise ValueError('the batch to refill has another layout (geometry or order of the images)')
+            groups = [JpegGroup(g, idx, torch.cuda.is_available()) for g, idx in layout]
+        jobs = [(grp, k, i) for grp in groups for k, i in enumerate(grp.indices)]
+
+        def decode(job):
+            grp, k, i = job
+            h = _lib.JpegHeader()
+            return lib.stp3_jpeg_entropy(streams[i], len(streams[i]), grp.coef[k].data_ptr(), grp.coef.shape[1],
+                                         grp.quant[k].data_ptr(), ctypes.byref(h))
+
+        for (grp, k, i), rc in zip(jobs, self._map(decode, jobs)):
+            if rc != 0:
+                raise _lib.Stp3HipError(f'image {i}: stp3_jpeg_entropy failed: {_lib._ERRORS.get(rc, rc)}')
+        sizes = [(f.height, f.width) if f is not None else None for f in infos]
+        for i, (_, s) in fallback.items():
+            sizes[i] = self._pillow_size(s)                                     # (the header only: Pillow decodes lazily)
+        return JpegBatch(len(streams), groups, fallback, sizes)
+
+    @staticmethod
+    def _pillow_open(data):
+        try:
+            from PIL import Image
+        except ImportError as e:
+            raise RuntimeError('Pillow is not installed: JpegDecoder.reference and the fallback for unsupported streams need it') from e
+        return Image.open(io.BytesIO(bytes(data)))
+
+    @classmethod
+    def _pillow(cls, data):
+        return np.asarray(cls._pillow_open(data).convert('RGB'))
+
+    @classmethod
+    def _pillow_size(cls, data):
+        width, height = cls._pillow_open(data).size
+        return (height, width)
+
+    def reference(self, streams):
+        """Pillow's decode of every stream, stacked: (N, H, W, 3) uint8 on the CPU."""
+        return torch.from_numpy(np.stack([self._pillow(s) for s in streams]))
+
+    # ---- the arithmetic of the kernel, stated with numpy --------------------------------------------------------------
+    @staticmethod
+    def _idct_pass(x, shift):
+        """One 8-point pass of jpeg_idct_islow (jidctint.c) along axis 1 of an int64 array."""
+        i0, i1, i2, i3, i4, i5, i6, i7 = (x[:, k] for k in range(8))
+        z1 = (i2 + i6) * 4433
+        tmp2, tmp3 = z1 - i6 * 15137, z1 + i2 * 6270
+        tmp0, tmp1 = (i0 + i4) * 8192, (i0 - i4) * 8192
+        tmp10, tmp13, tmp11, tmp12 = tmp0 + tmp3, tmp0 - tmp3, tmp1 + tmp2, tmp1 - tmp2
+        t0, t1, t2, t3 = i7, i5, i3, i1
+        z1, z2, z3, z4 = t0 + t3, t1 + t2, t0 + t2, t1 + t3
+        z5 = (z3 + z4) * 9633
+        t0, t1, t2, t3 = t0 * 2446, t1 * 16819, t2 * 25172, t3 * 12299
+        z1, z2, z3, z4 = z1 * -7373, z2 * -20995, z3 * -16069 + z5, z4 * -3196 + z5
+        t0, t1, t2, t3 = t0 + z1 + z3, t1 + z2 + z4, t2 + z2 + z3, t3 + z1 + z4
+        rows = (tmp10 + t3, tmp11 + t2, tmp12 + t1, tmp13 + t0, tmp13 - t0, tmp12 - t1, tmp11 - t2, tmp10 - t3)
+        # (the kernel forms the sums in 32 bits, two's complement: the same bits wherever int32 does not overflow)
+        wrap = lambda v: ((v + (1 << 31)) & 0xFFFFFFFF) - (1 << 31)
+        return np.stack([wrap(r + (1 << (shift - 1))) >> shift for r in rows], axis=1)
+
+    @classmethod
+    def _plane(cls, coef, quant, by, bx):
+        """(by * bx * 64,) coefficients + a (64,) table -> the (by * 8, bx * 8) samples of the padded block grid."""
+        x = coef.reshape(-1, 8, 8).astype(np.int64) * quant.reshape(1, 8, 8).astype(np.int64)
+        ws = cls._idct_pass(x, 13 - 2)                                           # columns: along the row index
+        px = cls._idct_pass(ws.transpose(0, 2, 1), 13 + 2 + 3).transpose(0, 2, 1)   # rows
+        i = px & 1023                                                             # the range-limit table of jdmaster.c
+        s = np.where(i < 128, i + 128, np.where(i < 512, 255, np.where(i < 896, 0, i - 896)))
+        return s.reshape(by, bx, 8, 8).transpose(0, 2, 1, 3).reshape(by * 8, bx * 8)
+
+    @staticmethod
+    def _upsample_h(s, rounding_even, rounding_odd, shift, edge):
+        """The horizontal triangle filter of h2v1 (on samples) / h2v2 (on column sums) over the true width."""
+        wc = s.shape[1]
+        last, nxt = np.concatenate([s[:, :1], s[:, :-1]], 1), np.concatenate([s[:, 1:], s[:, -1:]], 1)
+        even, odd = (3 * s + last + rounding_even) >> shift, (3 * s + nxt + rounding_odd) >> shift
+        even[:, 0], odd[:, -1] = edge(s[:, 0], rounding_even), edge(s[:, -1], rounding_odd)
+        return np.stack([even, odd], axis=2).reshape(s.shape[0], 2 * wc)
+
+    @classmethod
+    def _image(cls, g, coef, quant):
+        mx, my = -(-g.width // (8 * g.hs)), -(-g.height // (8 * g.vs))
+        n_y = mx * g.hs * my * g.vs * 64
+        luma = cls._plane(coef[:n_y], quant[0], my * g.vs, mx * g.hs)[:g.height, :g.width]
+        if g.components == 1:
+            return np.repeat(luma[:, :, None], 3, axis=2).astype(np.uint8)
+        wc, hc = -(-g.width // g.hs), -(-g.height // g.vs)
+        chroma = []
+        for c in (1, 2):
+            s = cls._plane(coef[n_y + (c - 1) * mx * my * 64:n_y + c * mx * my * 64], quant[c], my, mx)[:hc, :wc]
+            if g.hs == 2 and wc <= 2:                                            # jdsample.c: no fancy up-sampling this narrow
+                s = np.repeat(np.repeat(s, g.vs, axis=0), 2, axis=1)
+            elif g.hs == 2 and g.vs == 1:
+                s = cls._upsample_h(s, 1, 2, 2, lambda v, r: v)
+            elif g.hs == 2:
+                up, down = np.concatenate([s[:1], s[:-1]]), np.concatenate([s[1:], s[-1:]])
+                sums = np.stack([3 * s + up, 3 * s + down], axis=1).reshape(2 * hc, wc)
+                s = cls._upsample_h(sums, 8, 7, 4, lambda v, r: (4 * v + r) >> 4)
+            chroma.append(s[:g.height, :g.width] - 128)
+        u, v = chroma
+        rgb = np.stack([luma + ((91881 * v + 32768) >> 16), luma + ((-22554 * u + 32768 - 46802 * v) >> 16),
+                        luma + ((116130 * u + 32768) >> 16)], axis=2)
+        return rgb.clip(0, 255).astype(np.uint8)
+
+    def reconstruct_reference(self, batch):
+        """The kernel's integer arithmetic on the CPU (what CPU tensors take): (N, H, W, 3) uint8, or a list of (H, W, 3)
+        tensors when the images of the batch differ in size."""
+        images = [None] * batch.n
+        for grp in batch.groups:
+            coef, quant = grp.coef.numpy(), grp.quant.numpy().view(np.uint16)
+            for k, i in enumerate(grp.indices):
+                images[i] = torch.from_numpy(self._image(grp.geometry, coef[k], quant[k]))
+        for i, (_, s) in batch.fallback.items():
+            images[i] = torch.from_numpy(self._pillow(s).copy())
+        return torch.stack(images) if len(set(batch.sizes)) == 1 else images
+
+    # ---- device -------------------------------------------------------------------------------------------------------
+    def reconstruct_device(self, geometry, coef, quant, out=None):
+        """The kernel alone on tensors that already are on the GPU -- coef (N, coef_count) int16, quant (N, 3, 64) 16-bit --
+        into ``out`` (N, H, W, 3) uint8: no copy, no allocation when ``out`` is given (what a captured graph holds)."""
+        g = geometry
+        n = coef.shape[0]
+        if coef.dtype != torch.int16 or quant.element_size() != 2 or tuple(coef.shape) != (n, _coef_count(g)) or \
+                tuple(quant.shape) != (n, 3, 64) or not coef.is_contiguous() or not quant.is_contiguous():
+            raise ValueError('coef must be (N, coef_count) int16 and quant (N, 3, 64) 16-bit, both contiguous')
+        ops._need_gpu(coef, quant)
+        if out is None:
+            out = torch.empty(n, g.height, g.width, 3, dtype=torch.uint8, device=coef.device)
+        if out.dtype != torch.uint8 or tuple(out.shape) != (n, g.height, g.width, 3) or not out.is_contiguous():
+            raise ValueError(f'out must be a contiguous uint8 tensor of shape {(n, g.height, g.width, 3)}')
+        ops._need_gpu(out)
+        d = _lib.JpegDims(n, g.width, g.height, g.components, g.hs, g.vs)
+        _lib.check(_lib.lib().stp3_jpeg_reconstruct(ctypes.byref(d), ops._ptr(coef), ops._ptr(quant), ops._ptr(out), ops._stream()),
+                   'stp3_jpeg_reconstruct')
+        return out
+
+    def reconstruct(self, batch, device, out=None):
+        """One non-blocking host-to-device copy of the coefficients and one launch per geometry; streams behind the fallback
+        are uploaded as Pillow decoded them.  (N, H, W, 3) uint8 on ``device`` (into ``out`` when given), or a list of
+        (H, W, 3) tensors in the order of the call when the images differ in size."""
+        dev = torch.device(device)
+        stacked = len(set(batch.sizes)) == 1
+        if out is not None and (not stacked or tuple(out.shape) != (batch.n,) + tuple(batch.sizes[0]) + (3,) or out.dtype != torch.uint8
+                                or out.device.type != dev.type or not out.is_contiguous()):
+            raise ValueError('out must be a contiguous uint8 tensor (N, H, W, 3) on the device of the call')
+        staged = [(grp, grp.coef.to(dev, non_blocking=True), grp.quant.to(dev, non_blocking=True)) for grp in batch.groups]
+        if staged and not staged[0][1].is_cuda or not staged and dev.type != 'cuda':
+            ref = self.reconstruct_reference(batch)
+            if out is not None:
+                out.copy_(ref)
+            return out if out is not None else ref
+        if stacked and out is None:
+            out = torch.empty((batch.n,) + tuple(batch.sizes[0]) + (3,), dtype=torch.uint8, device=dev)
+        images = [None] * batch.n
+        for grp, coef, quant in staged:
+            first = grp.indices[0]
+            if stacked and grp.indices == list(range(first, first + len(grp.indices))):
+                self.reconstruct_device(grp.geometry, coef, quant, out[first:first + len(grp.indices)])
+                continue
+            part = self.reconstruct_device(grp.geometry, coef, quant)
+            if stacked:
+                out.index_copy_(0, torch.tensor(grp.indices, device=dev), part)
+            for k, i in enumerate(grp.indices):
+                images[i] = part[k]
+        for i, (_, s) in batch.fallback.items():
+            host = torch.from_numpy(self._pillow(s).copy())
+            if stacked:
+                out[i].copy_(host, non_blocking=True)
+            else:
+                images[i] = host.to(dev)
+        return out if stacked else images
+
+    def __call__(self, streams, device, out=None):
+        return self.reconstruct(self.entropy(streams), device, out=out)
