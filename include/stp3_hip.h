@@ -1503,6 +1503,34 @@ int stp3_carla_topdown(int32_t n, int32_t Ht, int32_t Wt, int32_t Hr, int32_t Wr
                        const int32_t* col_src, int32_t out_kind, const uint8_t* frames, void* vehicle, void* pedestrian,
                        void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * PNG scanlines (csrc/stp3_png.hip; stp3_amd.datas.PngDecoder): the Image.open(...) in front of every entry above --
+ * get_hdmap / get_labels, stp3/datas/CarlaData.py:240-266, and the camera and depth files of __getitem__, :377-397 -- split
+ * where a PNG decode is serial.  The HOST parses the chunks and inflates the IDAT data (Python: struct + zlib, no C of this
+ * library); undoing the per-scanline filters runs in ONE kernel for all n images of a geometry, byte for byte what Pillow
+ * (or any conforming decoder) returns.  Restated from the PNG specification, section 9 (filter types 0 .. 4).
+ *
+ * stp3_png_unfilter   rows [n][height][1 + width * bpp] uint8 IN DEVICE MEMORY, as inflate wrote them: per scanline one filter
+ *                     byte, then the filtered bytes, no padding (scanlines therefore start at any alignment).  bpp = bytes per
+ *                     pixel, 1 .. 4 (8-bit grey or palette index, grey + alpha, RGB, RGBA).  out [n][height][width * bpp] uint8,
+ *                     contiguous.  Per byte, with a = the reconstructed byte bpp to the left (0 for x < bpp), b = the byte above
+ *                     (0 in row 0), c = the byte above-left (0 in row 0 or for x < bpp), all sums modulo 256: 0 None adds 0,
+ *                     1 Sub adds a, 2 Up adds b, 3 Average adds (a + b) >> 1 of the 9-bit sum, 4 Paeth adds a if
+ *                     |p - a| <= |p - b| and |p - a| <= |p - c| for p = a + b - c, else b if |p - b| <= |p - c|, else c.
+ *                     The kernel is TOTAL: a filter byte above 4 (the host refuses such a stream before it gets here) adds 0,
+ *                     and no input byte enters an address.  One workgroup of up to 8 waves per image; a wave owns a band of
+ *                     64 rows, lane l at pixel s - l in step s, each wave 80 steps behind the wave of the band above; the
+ *                     last row of a band reaches the next wave through a ring in LDS, the last row of 512 rows waits in
+ *                     LDS (4 bytes per pixel) for the next pass.  Waves meet at __syncthreads only, nothing spins.  Width
+ *                     and height limit: 16 384 (the carry row is 64 KB of LDS there, 104 KB in all for an RGBA image of
+ *                     449 rows or more; the limit of dynamic LDS is raised once per device to that, so calls from several
+ *                     host threads do not disturb each other); there is no narrower limit of the design.
+ * Re-entrant, only enqueues on `stream`, allocates nothing, reads nothing from the host and does not synchronise: it can be
+ * captured, and a replay after both buffers were rewritten decodes the new images.
+ * STP3_EINVAL: a null pointer, n or a size < 1, bpp outside 1 .. 4;  STP3_EUNSUP: a side above 16 384 (any n is taken: one
+ * workgroup per image). */
+int stp3_png_unfilter(const uint8_t* rows, int32_t n, int32_t height, int32_t width, int32_t bpp, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -431,6 +431,7 @@ SIGNATURES = {
     'stp3_carla_depth': (c_int, [c_int32] * 6 + [c_double] * 2 + [c_void_p] * 3),
     'stp3_carla_hdmap': (c_int, [c_int32] * 5 + [c_void_p] * 3),
     'stp3_carla_topdown': (c_int, [c_int32] * 6 + [c_void_p] * 2 + [c_int32] + [c_void_p] * 4),
+    'stp3_png_unfilter': (c_int, [c_void_p] + [c_int32] * 4 + [c_void_p] * 2),
 }
 
 _lib = None

@@ -1,8 +1,10 @@
 """The CARLA half of the reference: recorded samples (``stp3/datas/CarlaData.py``) and the closed-loop tick (``carla_agent.py``)
 from decoded bytes to tensors and from tensors to steer / throttle / brake.
 
-The host's work ends at decoded bytes (PNG decoding, the directory scan of ``get_train_val`` and the simulator classes stay
-outside).  Everything from bytes to tensors is ONE launch per kind for all frames and cameras of a call (csrc/stp3_carla.hip):
+``CarlaDecoder`` starts at decoded bytes (the directory scan of ``get_train_val`` and the simulator classes stay outside);
+``load_carla_sample`` starts at the PNG files' bytes, with ``datas.PngDecoder`` -- chunks and zlib on host threads, the scanline
+filters in a kernel -- in front.  Everything from bytes to tensors is ONE launch per kind for all frames and cameras of a call
+(csrc/stp3_carla.hip):
 
     dec = CarlaDecoder(cfg)                                  # or crop=256, bev_crop=200, topdown_scale=1.1, downsample=, d_bound=
     x = dec.images(frames, order='rgb')                      # (..., Hs, Ws, 3 | 4) uint8 -> (..., 3, crop, crop) float32 | bf16
@@ -400,6 +402,46 @@ def assemble_carla_sample(decoder, images, depths, hdmaps, topdowns, seq_x, seq_
     steering = torch.tensor([steer], dtype=torch.float64, device=dev)
     data['sample_trajectory'] = trajectory_sampling(speed, steering, s - t, sample_num, draws=draws, generator=generator)[0]
     return data
+
+
+def _decode_kind(png, files, what, three_channels, device):
+    """All PNG files of one kind in one call of ``png``: a stacked uint8 tensor (len(files), H, W[, 3]) on ``device``."""
+    if not files:
+        raise ValueError(f'load_carla_sample: no {what} files')
+    batch = png.inflate(files)
+    for i, shape in enumerate(batch.shapes):
+        if three_channels and (len(shape) != 3 or shape[2] != 3):
+            raise ValueError(f'load_carla_sample: {what} file {i} decodes to {shape}, an RGB image (H, W, 3) is expected')
+        if not three_channels and len(shape) != 2:
+            raise ValueError(f'load_carla_sample: {what} file {i} decodes to {shape}, a 2-D image of class ids is expected')
+        if shape != batch.shapes[0]:
+            raise ValueError(f'load_carla_sample: {what} file {i} is {shape}, file 0 is {batch.shapes[0]}')
+    return png.unfilter(batch, device)
+
+
+def load_carla_sample(decoder, png, image_files, depth_files, hdmap_files, topdown_files, seq_x, seq_y, seq_theta, x_command,
+                      y_command, command, steer, throttle, brake, velocity, receptive_field, sample_num, draws=None, generator=None,
+                      device='cuda'):
+    """``CarlaDataset.__getitem__`` (CarlaData.py:355-450) from the files' BYTES: ``assemble_carla_sample`` with a
+    ``datas.PngDecoder`` in front of it instead of ``Image.open`` per file (CarlaData.py:240-266,377-397).
+
+    image_files, depth_files: T rows of 4 PNG byte strings (front, left, right, rear) of the T = receptive_field past frames;
+    hdmap_files: T byte strings; topdown_files: S byte strings; the rest as ``assemble_carla_sample``.  Four calls of ``png``,
+    one per kind, each one host-to-device copy and one launch.  A camera, depth or hd-map file that is not RGB, or a top-down
+    file that is not a single-channel image, raises ``ValueError`` with the file's index (in row-major order of the argument)
+    -- the reference's own comparisons fail on such files."""
+    t = int(receptive_field)
+    cameras = [bytes(f) for row in image_files for f in row]
+    ranges = [bytes(f) for row in depth_files for f in row]
+    if len(cameras) != 4 * t or len(ranges) != 4 * t or any(len(row) != 4 for row in list(image_files) + list(depth_files)):
+        raise ValueError(f'load_carla_sample: {t} rows of 4 camera files and of 4 depth files expected')
+    images = _decode_kind(png, cameras, 'camera', True, device)
+    depths = _decode_kind(png, ranges, 'depth', True, device)
+    hdmaps = _decode_kind(png, list(hdmap_files), 'hd-map', True, device)
+    topdowns = _decode_kind(png, list(topdown_files), 'top-down', False, device)
+    return assemble_carla_sample(decoder, images.view(t, 4, *images.shape[1:]), depths.view(t, 4, *depths.shape[1:]), hdmaps, topdowns,
+                                 seq_x, seq_y, seq_theta, x_command, y_command, command, steer, throttle, brake, velocity,
+                                 receptive_field, sample_num, draws=draws, generator=generator)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------

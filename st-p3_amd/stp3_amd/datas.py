@@ -18,6 +18,10 @@ Lift-Splat augmentation the reference carries as ``img_transform`` (``stp3/utils
 ``JpegDecoder`` (at the end of the file) moves the boundary into the JPEG decoder: the Huffman bit stream of a baseline file is
 decoded on host threads, the rest of the decode is one kernel (``stp3_jpeg_reconstruct``) whose output, byte for byte Pillow's,
 is what the two classes above read.
+
+``PngDecoder`` (after it) is the same split for the PNG files of the CARLA loader: chunks and DEFLATE on host threads with the
+standard library's ``zlib``, the scanline filters in one kernel (``stp3_png_unfilter``), byte for byte Pillow's decode;
+``carla.load_carla_sample`` runs a sample from its files' bytes with it.
 """
 import collections
 import concurrent.futures
@@ -25,6 +29,8 @@ import ctypes
 import io
 import math
 import os
+import struct
+import zlib
 
 import numpy as np
 import torch
@@ -1679,3 +1685,312 @@ class JpegDecoder:
 
     def __call__(self, streams, device, out=None):
         return self.reconstruct(self.entropy(streams), device, out=out)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# PNG images of the CARLA loader: chunks and DEFLATE on host threads (struct + zlib of the standard library), the scanline
+# filters in one kernel (csrc/stp3_png.hip: stp3_png_unfilter), byte-exact with Pillow's decode.  Its output is what
+# carla.CarlaDecoder reads (carla.load_carla_sample).
+# ----------------------------------------------------------------------------------------------------------------------
+class PngUnsupported(ValueError):
+    """A stream the decoder does not take (bit depth 1 / 2 / 4 / 16, Adam7, APNG, a side above 16 384) met with ``fallback=False``."""
+
+
+PngGeometry = collections.namedtuple('PngGeometry', 'height width bpp')
+PngInfo = collections.namedtuple('PngInfo', 'width height bit_depth colour_type interlace bpp shape idat')
+_PNG_SIGNATURE = b'\x89PNG\r\n\x1a\n'
+_PNG_CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}                              # colour type -> samples per pixel
+_PNG_DEPTHS = {0: (1, 2, 4, 8, 16), 2: (8, 16), 3: (1, 2, 4, 8), 4: (8, 16), 6: (8, 16)}
+_PNG_CHECKED = (b'IHDR', b'PLTE', b'IDAT', b'IEND')                         # the chunks whose CRC is verified
+_PNG_MAX_SIDE = 16384
+_PNG_PILLOW_BYTE_MODES = ('1', 'L', 'LA', 'P', 'PA', 'RGB', 'RGBA')         # what the fallback can put into a uint8 result
+
+
+def _png_shape(g):
+    return (g.height, g.width) if g.bpp == 1 else (g.height, g.width, g.bpp)
+
+
+class PngGroup:
+    """The images of a ``PngBatch`` that share one geometry: where they sit in the call and their scanlines as inflate wrote
+    them, (n, H, 1 + W * bpp) uint8 -- one filter byte, then the filtered bytes, no padding --, pinned where there is a GPU."""
+
+    def __init__(self, geometry, indices, pin):
+        self.geometry, self.indices = geometry, list(indices)
+        self.rows = torch.empty(len(self.indices), geometry.height, 1 + geometry.width * geometry.bpp, dtype=torch.uint8,
+                                pin_memory=pin)
+
+
+class PngBatch:
+    """What ``PngDecoder.inflate`` returns: per geometry a ``PngGroup``; ``fallback`` maps the index of every stream the
+    decoder does not take to (reason, its bytes) -- Pillow decodes those on the host; ``shapes``: the decoded shape per image."""
+
+    def __init__(self, n, groups, fallback, shapes):
+        self.n, self.groups, self.fallback, self.shapes = n, groups, fallback, shapes
+
+    def layout(self):
+        return [(g.geometry, tuple(g.indices)) for g in self.groups]
+
+
+class PngDecoder:
+    """PNG bytes -> uint8 tensors on the GPU, equal to ``np.asarray(PIL.Image.open(...))`` byte for byte: (H, W) for grey and
+    palette images (the palette INDICES, Pillow's mode ``P``), (H, W, C) for grey + alpha, RGB and RGBA.
+
+        png = PngDecoder()
+        frames = png(list_of_bytes, 'cuda')                 # chunks + inflate on host threads, one kernel per geometry
+        x = carla.CarlaDecoder(cfg).images(frames)          # (carla.load_carla_sample does a whole sample)
+
+    Taken: 8-bit samples, not interlaced, colour types 0, 2, 3, 4, 6, sides up to 16 384.  ``workers``: host threads of the
+    inflate (zlib releases the interpreter lock), at most ``min(16, os.cpu_count())`` by default.  ``fallback``: a stream of
+    another bit depth, an Adam7 stream, an APNG or a larger one is decoded by Pillow on the host and uploaded into the same slot
+    of the result; ``fallback=False`` raises ``PngUnsupported`` instead.  That is decided from the headers, before anything is
+    inflated.  The result is uint8 throughout: a 1-bit image, which Pillow hands out as booleans, arrives as 0 / 1, and a
+    stream Pillow decodes to more than 8 bits per sample (16-bit grey: ``I;16``) raises ``PngUnsupported`` whatever ``fallback``
+    is -- it is never cut to 8 bits (Pillow itself reduces 16-bit RGB, RGBA and grey + alpha to 8 bits; those take the fallback).  A corrupt stream always raises ``Stp3HipError`` and is NOT handed to Pillow: a bad signature, a chunk that runs
+    past the file, a wrong CRC of IHDR / PLTE / IDAT / IEND (ancillary chunks are skipped unread), a zlib error or a zlib
+    stream without its end, an inflated length other than H * (1 + W * bpp), a filter byte above 4.  This is stricter than
+    Pillow on purpose: Pillow 12.2 accepts a stream whose data ends one scanline early and pads the missing row; this decoder
+    refuses it."""
+
+    def __init__(self, workers=None, fallback=True):
+        self.workers = max(1, int(workers)) if workers is not None else min(16, os.cpu_count() or 1)
+        self.fallback = fallback
+        self._pool = None
+
+    _map = JpegDecoder._map
+
+    # ---- host ---------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def info(data):
+        """The header and the concatenated IDAT payloads of one stream.  Raises ``PngUnsupported`` as soon as the headers say
+        so, ``Stp3HipError`` for a malformed stream."""
+        data = bytes(data)
+        bad = lambda what: _lib.Stp3HipError(f'PNG: {what}')
+        if data[:8] != _PNG_SIGNATURE:
+            raise bad('bad signature')
+        pos, header, idat, ended = 8, None, [], False
+        while not ended:
+            if pos + 12 > len(data):
+                raise bad('truncated: a chunk header runs past the data (no IEND)')
+            length, kind = struct.unpack_from('>I4s', data, pos)
+            if pos + 12 + length > len(data):
+                raise bad(f'truncated: chunk {kind!r} runs past the data')
+            body = data[pos + 8:pos + 8 + length]
+            if (header is None) != (kind == b'IHDR'):
+                raise bad('IHDR must be the first chunk and the only one of its kind')
+            if kind in _PNG_CHECKED and zlib.crc32(body, zlib.crc32(kind)) != struct.unpack_from('>I', data, pos + 8 + length)[0]:
+                raise bad(f'CRC of chunk {kind.decode()} is wrong')
+            if kind == b'IHDR':
+                if length != 13:
+                    raise bad('IHDR of another length than 13')
+                header = struct.unpack('>IIBBBBB', body)
+                width, height, depth, colour, compression, filtering, interlace = header
+                if (width < 1 or height < 1 or width >= 1 << 31 or height >= 1 << 31 or colour not in _PNG_CHANNELS or
+                        depth not in _PNG_DEPTHS[colour] or compression != 0 or filtering != 0 or interlace > 1):
+                    raise bad(f'illegal IHDR {header}')
+                if depth != 8:
+                    raise PngUnsupported(f'{depth}-bit samples')
+                if interlace:
+                    raise PngUnsupported('Adam7 interlace')
+                if max(width, height) > _PNG_MAX_SIDE:
+                    raise PngUnsupported('a side above 16 384 pixels')
+            elif kind == b'acTL':
+                raise PngUnsupported('an animated PNG (acTL)')
+            elif kind == b'IDAT':
+                idat.append(body)
+            elif kind == b'IEND':
+                ended = True
+            pos += 12 + length
+        if not idat:
+            raise bad('no IDAT chunk')
+        bpp = _PNG_CHANNELS[colour]
+        return PngInfo(width, height, depth, colour, interlace, bpp, _png_shape(PngGeometry(height, width, bpp)), b''.join(idat))
+
+    def inflate(self, streams, out=None):
+        """Parse and inflate ``streams`` (bytes-like objects) into a ``PngBatch``; ``out``: a batch of the same layout to refill."""
+        streams = [s if isinstance(s, bytes) else bytes(s) for s in streams]
+
+        def header(s):
+            try:
+                return self.info(s)
+            except (PngUnsupported, _lib.Stp3HipError) as e:
+                return e
+
+        infos, fallback = self._map(header, streams), {}
+        for i, f in enumerate(infos):
+            if isinstance(f, PngUnsupported):
+                if not self.fallback:
+                    raise PngUnsupported(f'image {i}: {f}') from None
+                fallback[i] = (str(f), streams[i])
+                infos[i] = None
+            elif isinstance(f, Exception):
+                raise _lib.Stp3HipError(f'image {i}: {f}') from None
+        order = {}
+        for i, f in enumerate(infos):
+            if f is not None:
+                order.setdefault(PngGeometry(f.height, f.width, f.bpp), []).append(i)
+        layout = [(g, tuple(idx)) for g, idx in order.items()]
+        if out is not None and out.layout() == layout and out.n == len(streams):
+            groups = out.groups
+        else:
+            if out is not None:
+                raise ValueError('the batch to refill has another layout (geometry or order of the images)')
+            groups = [PngGroup(g, idx, torch.cuda.is_available()) for g, idx in layout]
+        jobs = [(grp, k, i) for grp in groups for k, i in enumerate(grp.indices)]
+
+        def decode(job):
+            grp, k, i = job
+            g = grp.geometry
+            want = g.height * (1 + g.width * g.bpp)
+            z = zlib.decompressobj()
+            try:
+                raw = z.decompress(infos[i].idat, want + 1)                     # (bounded: a stream cannot inflate without end)
+            except zlib.error as e:
+                return f'zlib: {e}'
+            if len(raw) != want:
+                return f'{"more than " if len(raw) > want else ""}{len(raw)} bytes inflated, {g.height} scanlines of {1 + g.width * g.bpp} expected'
+            if not z.eof:
+                return 'the zlib stream has no end (truncated, or its checksum is missing)'
+            rows = grp.rows[k].numpy()
+            rows.reshape(-1)[:] = np.frombuffer(raw, dtype=np.uint8)
+            worst = int(rows[:, 0].max())                                       # H filter bytes through a strided view
+            return f'filter type {worst}' if worst > 4 else None
+
+        for (grp, k, i), err in zip(jobs, self._map(decode, jobs)):
+            if err is not None:
+                raise _lib.Stp3HipError(f'image {i}: PNG: {err}')
+        shapes = [f.shape if f is not None else None for f in infos]
+        for i, (reason, s) in fallback.items():
+            try:
+                shapes[i] = self._pillow_shape(s)
+            except PngUnsupported as e:
+                raise PngUnsupported(f'image {i}: {reason}, and {e}') from None
+        return PngBatch(len(streams), groups, fallback, shapes)
+
+    @staticmethod
+    def _pillow_open(data):
+        try:
+            from PIL import Image
+        except ImportError as e:
+            raise RuntimeError('Pillow is not installed: PngDecoder.reference and the fallback for unsupported streams need it') from e
+        return Image.open(io.BytesIO(bytes(data)))
+
+    @classmethod
+    def _pillow(cls, data):
+        return np.asarray(cls._pillow_open(data))
+
+    @classmethod
+    def _pillow_bytes(cls, data):
+        """Pillow's decode of a stream behind the fallback as uint8 (a 1-bit image, which Pillow hands out as booleans: 0 / 1)."""
+        array = cls._pillow(data)
+        if array.dtype == np.bool_:
+            array = array.astype(np.uint8)
+        if array.dtype != np.uint8:
+            raise PngUnsupported(f'Pillow decodes it to {array.dtype}, which the uint8 result cannot hold')
+        return torch.from_numpy(np.ascontiguousarray(array).copy())
+
+    @classmethod
+    def _pillow_shape(cls, data):
+        im = cls._pillow_open(data)                                              # (the header only: Pillow decodes lazily)
+        if im.mode not in _PNG_PILLOW_BYTE_MODES:
+            raise PngUnsupported(f'Pillow decodes it to mode {im.mode!r}, more than 8 bits per sample, which the uint8 result cannot hold')
+        bands = len(im.getbands())
+        return (im.size[1], im.size[0]) if bands == 1 else (im.size[1], im.size[0], bands)
+
+    def reference(self, streams):
+        """Pillow's decode of every stream, ``np.asarray(Image.open(...))``: a list of arrays."""
+        return [self._pillow(s) for s in streams]
+
+    # ---- the arithmetic of the kernel, stated with numpy ------------------------------------------------------------
+    @staticmethod
+    def unfilter_reference(rows, bpp):
+        """(n, H, 1 + W * bpp) uint8 scanlines -> (n, H, W * bpp) uint8, the filters of the PNG specification undone row by
+        row (what CPU tensors take; a tensor gives a tensor, an array an array).  Sub is a prefix sum per channel and Up an
+        addition of the finished row above, both modulo 256; Average and Paeth are recurrences and loop over the bytes."""
+        src = rows.numpy() if torch.is_tensor(rows) else np.asarray(rows)
+        if src.dtype != np.uint8 or src.ndim != 3 or bpp not in (1, 2, 3, 4) or (src.shape[2] - 1) % bpp or src.shape[2] < 1 + bpp:
+            raise ValueError('unfilter_reference: rows must be (n, H, 1 + W * bpp) uint8 with bpp in 1 .. 4')
+        n, h, line = src.shape[0], src.shape[1], src.shape[2] - 1
+        out = np.zeros((n, h, line), dtype=np.uint8)
+        for i in range(n):
+            above = np.zeros(line, dtype=np.uint8)
+            for r in range(h):
+                ft, raw = int(src[i, r, 0]), src[i, r, 1:]
+                if ft == 1:
+                    cur = np.cumsum(raw.reshape(-1, bpp), axis=0, dtype=np.uint8).reshape(-1)      # (uint8 sums wrap modulo 256)
+                elif ft == 2:
+                    cur = raw + above
+                elif ft in (3, 4):
+                    x, b, cur = raw.tolist(), above.tolist(), [0] * line
+                    for k in range(line):
+                        a = cur[k - bpp] if k >= bpp else 0
+                        if ft == 3:
+                            pred = (a + b[k]) >> 1
+                        else:
+                            c = b[k - bpp] if k >= bpp else 0
+                            p = a + b[k] - c
+                            pa, pb, pc = abs(p - a), abs(p - b[k]), abs(p - c)
+                            pred = a if pa <= pb and pa <= pc else b[k] if pb <= pc else c
+                        cur[k] = (x[k] + pred) & 255
+                    cur = np.array(cur, dtype=np.uint8)
+                else:                                                            # None; the kernel treats a type above 4 alike
+                    cur = raw
+                out[i, r] = cur
+                above = out[i, r]
+        return torch.from_numpy(out) if torch.is_tensor(rows) else out
+
+    # ---- device -----------------------------------------------------------------------------------------------------
+    def unfilter_device(self, geometry, rows, out=None):
+        """The kernel alone on tensors that already are on the GPU -- rows (n, H, 1 + W * bpp) uint8 -- into ``out`` (n, H, W)
+        (bpp 1) or (n, H, W, bpp) uint8: no copy, no allocation when ``out`` is given (what a captured graph holds)."""
+        g = geometry
+        n = rows.shape[0] if rows.dim() == 3 else 0
+        if rows.dtype != torch.uint8 or tuple(rows.shape) != (n, g.height, 1 + g.width * g.bpp) or n < 1 or not rows.is_contiguous():
+            raise ValueError(f'rows must be a contiguous uint8 tensor (n, {g.height}, {1 + g.width * g.bpp})')
+        ops._need_gpu(rows)
+        shape = (n,) + _png_shape(g)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=rows.device)
+        if out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f'out must be a contiguous uint8 tensor of shape {shape}')
+        ops._need_gpu(out)
+        _lib.check(_lib.lib().stp3_png_unfilter(ops._ptr(rows), n, g.height, g.width, g.bpp, ops._ptr(out), ops._stream()),
+                   'stp3_png_unfilter')
+        return out
+
+    def unfilter(self, batch, device, out=None):
+        """One non-blocking host-to-device copy of the scanlines and one launch per geometry; streams behind the fallback are
+        uploaded as Pillow decoded them.  One uint8 tensor (N, H, W[, C]) on ``device`` (``out`` when given) when all images
+        have one shape, else a list of tensors in the order of the call."""
+        dev = torch.device(device)
+        stacked = len(set(batch.shapes)) == 1
+        shape = (batch.n,) + tuple(batch.shapes[0]) if stacked else None
+        if out is not None and (not stacked or tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device.type != dev.type
+                                or not out.is_contiguous()):
+            raise ValueError('out must be a contiguous uint8 tensor (N, H, W[, C]) on the device of the call')
+        if stacked and out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=dev)
+        images = [None] * batch.n
+        for grp in batch.groups:
+            first, count = grp.indices[0], len(grp.indices)
+            whole = stacked and grp.indices == list(range(first, first + count))
+            if dev.type != 'cuda':
+                part = self.unfilter_reference(grp.rows, grp.geometry.bpp).view((count,) + _png_shape(grp.geometry))
+                if whole:
+                    out[first:first + count].copy_(part)
+            else:
+                rows = grp.rows.to(dev, non_blocking=True)
+                part = self.unfilter_device(grp.geometry, rows, out[first:first + count] if whole else None)
+            if stacked and not whole:
+                out.index_copy_(0, torch.tensor(grp.indices, device=dev), part)
+            for k, i in enumerate(grp.indices):
+                images[i] = part[k]
+        for i, (_, s) in batch.fallback.items():
+            host = self._pillow_bytes(s)
+            if stacked:
+                out[i].copy_(host, non_blocking=True)
+            else:
+                images[i] = host.to(dev)
+        return out if stacked else images
+
+    def __call__(self, streams, device, out=None):
+        return self.unfilter(self.inflate(streams), device, out=out)
