@@ -1151,6 +1151,89 @@ int stp3_jpeg_reconstruct(const stp3_jpeg_dims* dims, const int16_t* coef, const
                           void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * JPEG camera frames, the Huffman scan ON THE DEVICE (csrc/stp3_jpeg_entropy.h: stp3_jpeg_scan_prepare;
+ * csrc/stp3_jpeg_huff.hip): a second way to the coefficient and table buffers of stp3_jpeg_reconstruct, equal to what
+ * stp3_jpeg_entropy writes element for element, padding blocks included.  The host decoder stays the statement of the
+ * result; this path never guesses -- whatever it does not decode cleanly is reported and belongs to stp3_jpeg_entropy.
+ * Restated from published sources: jdhuff.c (the look-ahead tables and the symbol decode, as above) and, for the parallel
+ * scheme, Klein & Wiseman, "Parallel Huffman decoding with applications to JPEG files" (The Computer Journal 46(5), 2003:
+ * a decoder started at a wrong bit falls into step with the right one after a few codes) and Weissenberger & Schmidt,
+ * "Massively parallel Huffman decoding on GPUs" (ICPP 2018: subsequences, one thread each, overflow into the neighbours
+ * until the recorded state repeats, a prefix sum for the output positions, a second decode that writes).
+ *
+ * Host: stp3_jpeg_scan_prepare parses the headers exactly as stp3_jpeg_info does (the same STP3_EUNSUP / STP3_EINVAL),
+ *   then walks the entropy-coded bytes ONCE (memchr for 0xFF, block copies) and writes into `scan_out` (room for
+ *   scan_capacity bytes; stp3_jpeg_scan_bytes(header, len) is an upper bound):
+ *     [seg_offset]     nseg x {first subsequence, bit length, first MCU} int32 -- one SEGMENT per restart interval (a
+ *                      stream without restart markers: one), in stream order
+ *     [scan_offset]    nsub subsequences of STP3_JPEG_SUB_BYTES bytes: the scan WITHOUT byte stuffing and without the
+ *                      markers, every segment padded with zeros to whole subsequences (at least one)
+ *     [subseg_offset]  nsub int32: the segment of every subsequence
+ *   and fills `desc`: those offsets and counts, the look-ahead tables as the host decoder builds them (at most two DC and
+ *   two AC tables), the table index per component, the quantisers in ZIGZAG order (for the 16-bit bound) and the MCU
+ *   layout.  quant: [3][64] uint16 in natural order, as stp3_jpeg_entropy writes it.  STP3_JPEG_IRREGULAR (not an error:
+ *   the caller gives the stream to stp3_jpeg_entropy): a marker in the scan other than the RSTn expected in sequence, no
+ *   EOI, fill bytes (0xFF 0xFF) or an 0xFF at the very end, a segment count that differs from what restart_interval and
+ *   the MCU count give, more than two tables of a class, more than 65 536 segments or 2^27 bytes.  (Junk bytes in front
+ *   of a marker are indistinguishable from data here: the device decode reports such a stream, see below.)  STP3_EINVAL
+ *   also for a null pointer or a scan_capacity too small.  Every read is checked against len, every write against
+ *   scan_capacity; nothing is allocated, no state is kept.
+ *
+ * Device: stp3_jpeg_entropy_device, all N images of one geometry per call.
+ *   scans   [N][scan_stride] bytes in device memory, image n as stp3_jpeg_scan_prepare wrote it (scan_stride: a multiple
+ *           of 4, at least every image's used_bytes)
+ *   descs   [N] stp3_jpeg_scan_desc in device memory
+ *   coef    [N][coef_count] int16, as stp3_jpeg_entropy writes them (cleared first by the call)
+ *   status  [N] int32: 0 decoded; STP3_JPEG_NOT_CONVERGED the subsequences had not fallen into step after `sync_rounds`
+ *           further launches; STP3_EINVAL a code no table assigns, a run past coefficient 63, a coefficient or a running DC
+ *           whose dequantised value leaves 16 bits, a bit consumed behind a segment's end, a segment that does not end
+ *           inside its last byte with exactly its MCUs, or a descriptor that does not fit scan_stride / max_subs /
+ *           max_segs.  The coefficients of an image whose status is not 0 are unspecified: decode it with stp3_jpeg_entropy.
+ *   workspace  stp3_jpeg_entropy_workspace_bytes(dims, sync_rounds, &bytes) bytes of device memory.  Its first
+ *           N x (sync_rounds + 3) int32 are per image: [0 .. sync_rounds] whether launch r of the synchronisation still
+ *           changed a state another workgroup had consumed (the first zero: the rounds used), [sync_rounds + 1] the error
+ *           flag, [sync_rounds + 2] how many subsequences decoded more than one further subsequence before their state
+ *           repeated.
+ *   Passes: synchronise (one thread per subsequence, STP3_JPEG_SUB_THREADS subsequences per workgroup: decode from the
+ *   assumed state "first block of an MCU, DC expected", run on into the following subsequences until the state recorded
+ *   there repeats; across workgroups in at most sync_rounds further launches of the same step), a prefix sum of the blocks
+ *   completed per subsequence, a second decode that stores AC values and DC DIFFERENCES, an ordered scan of the DC
+ *   differences per component and segment, the status.  Every loop has a bound fixed by the host, no workgroup waits for
+ *   another, every store index is compared with coef_count.  Enqueues on `stream` only, allocates nothing, does not
+ *   synchronise.  STP3_EINVAL: a null pointer, dims outside what stp3_jpeg_reconstruct takes, scan_stride / max_subs /
+ *   max_segs < 1, sync_rounds outside [0, 64];  STP3_ENOSPACE: workspace_bytes too small. */
+#define STP3_JPEG_IRREGULAR      10011   /* stp3_jpeg_scan_prepare: a stream for the host decoder */
+#define STP3_JPEG_NOT_CONVERGED  10012   /* status word of stp3_jpeg_entropy_device */
+#define STP3_JPEG_SUB_BYTES      128     /* S: bytes of a subsequence */
+#define STP3_JPEG_SUB_THREADS    256     /* G: subsequences (threads) of a workgroup */
+typedef struct stp3_jpeg_huff_table {       /* csrc/stp3_jpeg_entropy.h: Huff */
+    uint16_t look[512];
+    int32_t maxcode[18];
+    int32_t valptr[17];
+    uint8_t vals[256];
+} stp3_jpeg_huff_table;
+typedef struct stp3_jpeg_scan_desc {
+    int32_t nsub, nseg;
+    int32_t seg_offset, scan_offset, subseg_offset, used_bytes;   /* bytes, inside the image's scan buffer */
+    int32_t components, hs, vs, mcus_x, mcus_y, restart_interval, coef_count;
+    int32_t dc_table[3], ac_table[3];       /* per component: index into dc[] / ac[] */
+    uint16_t quant[3][64];                  /* per component, zigzag order */
+    stp3_jpeg_huff_table dc[2], ac[2];
+} stp3_jpeg_scan_desc;
+typedef struct stp3_jpeg_huff_dims {
+    int32_t N, width, height, components, hs, vs;
+    int32_t scan_stride;                    /* bytes between the scan buffers of two images */
+    int32_t max_subs, max_segs;             /* the largest nsub / nseg of the call */
+} stp3_jpeg_huff_dims;
+size_t stp3_jpeg_scan_bytes(const stp3_jpeg_header* header, size_t len);
+int stp3_jpeg_scan_prepare(const uint8_t* data, size_t len, uint8_t* scan_out, size_t scan_capacity,
+                           stp3_jpeg_scan_desc* desc, uint16_t* quant);
+int stp3_jpeg_entropy_workspace_bytes(const stp3_jpeg_huff_dims* dims, int32_t sync_rounds, size_t* bytes);
+int stp3_jpeg_entropy_device(const stp3_jpeg_huff_dims* dims, const uint8_t* scans, const stp3_jpeg_scan_desc* descs,
+                             int16_t* coef, int32_t* status, void* workspace, size_t workspace_bytes, int32_t sync_rounds,
+                             void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Stand-alone voxel summing (csrc/stp3_voxsum.hip): the operator-level twin of the reference's
  * VoxelsSumming.forward / .backward (stp3/utils/geometry.py:302-318 / :320-330) for callers that hold the
  * rank-sorted row matrix; the fused path above never builds it.

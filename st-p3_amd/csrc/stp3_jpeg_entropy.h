@@ -390,4 +390,129 @@ inline int entropy(const uint8_t* data, size_t len, int16_t* coef, size_t coef_c
     return STP3_OK;
 }
 
+// ---- the scan prepared for the device decode (csrc/stp3_jpeg_huff.hip; include/stp3_hip.h, "the Huffman scan ON THE
+// DEVICE") -----------------------------------------------------------------------------------------------------------
+constexpr size_t kSubBytes = STP3_JPEG_SUB_BYTES;
+constexpr size_t kMaxSegments = 65536, kMaxScanLen = (size_t)1 << 27;      // bit positions stay inside 31 bits
+
+inline size_t segments_of(const stp3_jpeg_header& h) {
+    const size_t total = (size_t)h.mcus_x * (size_t)h.mcus_y;
+    return h.restart_interval > 0 ? (total + (size_t)h.restart_interval - 1) / (size_t)h.restart_interval : 1;
+}
+
+// an upper bound of what scan_prepare writes for a stream of `len` bytes with this header
+inline size_t scan_bytes(const stp3_jpeg_header& h, size_t len) {
+    const size_t nseg = segments_of(h), nsub = len / kSubBytes + nseg + 1;
+    return (nseg * 12 + kSubBytes) + nsub * kSubBytes + nsub * 4;
+}
+
+inline void copy_table(stp3_jpeg_huff_table* d, const Huff& s) {
+    memcpy(d->look, s.look, sizeof(d->look));
+    memcpy(d->maxcode, s.maxcode, sizeof(d->maxcode));
+    memset(d->valptr, 0, sizeof(d->valptr));
+    memcpy(d->valptr + 1, s.valptr + 1, 16 * sizeof(int32_t));  // ([0] is never set nor read)
+    memcpy(d->vals, s.vals, sizeof(d->vals));
+}
+
+// The entropy-coded bytes of the stream without byte stuffing, cut at the restart markers into segments padded to whole
+// subsequences, and the descriptor the device decode reads.  Nothing is decoded here, so nothing is guessed: whatever is
+// not "data, RSTn in sequence, data, ..., EOI" is STP3_JPEG_IRREGULAR and belongs to `entropy` above.
+inline int scan_prepare(const uint8_t* data, size_t len, uint8_t* out, size_t capacity, stp3_jpeg_scan_desc* desc,
+                        uint16_t* quant) {
+    if (!data || !out || !desc || !quant) return STP3_EINVAL;
+    Frame f;
+    Huff dc[4], ac[4];
+    for (int i = 0; i < 4; ++i) {
+        memset(&dc[i], 0, sizeof(Huff));
+        memset(&ac[i], 0, sizeof(Huff));
+    }
+    int tab[8];
+    size_t pos = 0;
+    const int rc = parse_headers(data, len, &f, dc, ac, tab, &pos);
+    if (rc != STP3_OK) return rc;
+    stp3_jpeg_header h;
+    fill_header(f, &h);
+    const size_t nseg = segments_of(h);
+    if (nseg > kMaxSegments || len > kMaxScanLen) return STP3_JPEG_IRREGULAR;
+    memset(desc, 0, sizeof(*desc));
+    int dc_slot[4] = {-1, -1, -1, -1}, ac_slot[4] = {-1, -1, -1, -1}, ndc = 0, nac = 0;
+    for (int c = 0; c < f.ncomp; ++c) {
+        const int td = tab[2 * c], ta = tab[2 * c + 1];
+        if (dc_slot[td] < 0) {
+            if (ndc == 2) return STP3_JPEG_IRREGULAR;
+            copy_table(&desc->dc[ndc], dc[td]);
+            dc_slot[td] = ndc++;
+        }
+        if (ac_slot[ta] < 0) {
+            if (nac == 2) return STP3_JPEG_IRREGULAR;
+            copy_table(&desc->ac[nac], ac[ta]);
+            ac_slot[ta] = nac++;
+        }
+        desc->dc_table[c] = dc_slot[td];
+        desc->ac_table[c] = ac_slot[ta];
+        memcpy(desc->quant[c], f.quant[f.tq[c]], 64 * sizeof(uint16_t));
+    }
+    for (int c = 0; c < 3; ++c) {
+        const uint16_t* q = f.quant[f.tq[c < f.ncomp ? c : 0]];
+        for (int k = 0; k < 64; ++k) quant[c * 64 + kNatural[k]] = q[k];
+    }
+    const size_t scan_off = (nseg * 12 + kSubBytes - 1) / kSubBytes * kSubBytes;
+    if (scan_off > capacity) return STP3_EINVAL;
+    const size_t room = capacity - scan_off;                    // for the subsequences and the table behind them
+    size_t w = 0, seg = 0;
+    for (;;) {
+        const size_t seg_start = w;
+        int marker = 0;
+        for (;;) {                                              // data up to the next marker
+            if (pos >= len) return STP3_JPEG_IRREGULAR;         // no EOI
+            const uint8_t* ff = static_cast<const uint8_t*>(memchr(data + pos, 0xFF, len - pos));
+            const size_t run = ff ? (size_t)(ff - (data + pos)) : len - pos;
+            if (run + 1 > room - w) return STP3_EINVAL;         // (w <= room throughout; + 1: a stuffed 0xFF may follow)
+            memcpy(out + scan_off + w, data + pos, run);
+            w += run;
+            pos += run;
+            if (!ff || pos + 1 >= len) return STP3_JPEG_IRREGULAR;   // the data runs into the end: no EOI
+            marker = data[pos + 1];
+            pos += 2;
+            if (marker != 0x00) break;
+            out[scan_off + w++] = 0xFF;                         // a stuffed 0xFF: data
+        }
+        const size_t bytes = w - seg_start;
+        const size_t padded = bytes ? (bytes + kSubBytes - 1) / kSubBytes * kSubBytes : kSubBytes;
+        if (padded > room - seg_start) return STP3_EINVAL;
+        memset(out + scan_off + w, 0, seg_start + padded - w);
+        w = seg_start + padded;
+        int32_t rec[3] = {(int32_t)(seg_start / kSubBytes), (int32_t)(bytes * 8),
+                          (int32_t)(seg * (size_t)(f.restart_interval > 0 ? f.restart_interval : 0))};
+        memcpy(out + seg * 12, rec, sizeof(rec));               // (seg < nseg: 12 * nseg <= scan_off <= capacity)
+        if (marker == 0xD9) {
+            if (seg + 1 != nseg) return STP3_JPEG_IRREGULAR;    // fewer restart intervals than the MCU count asks for
+            break;
+        }
+        if (marker != 0xD0 + (int)(seg & 7) || seg + 1 >= nseg) return STP3_JPEG_IRREGULAR;
+        ++seg;
+    }
+    const size_t nsub = w / kSubBytes;
+    if (nsub * 4 > room - w) return STP3_EINVAL;
+    for (size_t s = 0, i = 0; s < nseg; ++s) {
+        int32_t next = (int32_t)nsub;
+        if (s + 1 < nseg) memcpy(&next, out + (s + 1) * 12, 4);
+        for (const int32_t v = (int32_t)s; i < (size_t)next; ++i) memcpy(out + scan_off + w + i * 4, &v, 4);
+    }
+    desc->nsub = (int32_t)nsub;
+    desc->nseg = (int32_t)nseg;
+    desc->seg_offset = 0;
+    desc->scan_offset = (int32_t)scan_off;
+    desc->subseg_offset = (int32_t)(scan_off + w);
+    desc->used_bytes = (int32_t)(scan_off + w + nsub * 4);
+    desc->components = f.ncomp;
+    desc->hs = h.hs;
+    desc->vs = h.vs;
+    desc->mcus_x = h.mcus_x;
+    desc->mcus_y = h.mcus_y;
+    desc->restart_interval = f.restart_interval;
+    desc->coef_count = h.coef_count;
+    return STP3_OK;
+}
+
 }  // namespace stp3_jpeg

@@ -1449,6 +1449,36 @@ class JpegBatch:
         return [(g.geometry, tuple(g.indices)) for g in self.groups]
 
 
+class JpegScanGroup:
+    """The images of a ``JpegScanBatch`` that share one geometry, prepared for the device entropy decode: per image the scan
+    buffer stp3_jpeg_scan_prepare wrote (``scans`` (n, stride) uint8), its descriptor (``descs`` (n, sizeof desc) uint8) and
+    its quantisation tables (``quant`` (n, 3, 64)), pinned where there is a GPU.  ``host``: positions in the group whose stream
+    goes to the host decoder (STP3_JPEG_IRREGULAR)."""
+
+    def __init__(self, geometry, indices, stride, pin):
+        self.geometry, self.indices, self.stride = geometry, list(indices), stride
+        n = len(self.indices)
+        self.scans = torch.empty(n, stride, dtype=torch.uint8, pin_memory=pin)
+        self.descs = torch.zeros(n, ctypes.sizeof(_lib.JpegScanDesc), dtype=torch.uint8, pin_memory=pin)
+        self.quant = torch.empty(n, 3, 64, dtype=torch.int16, pin_memory=pin)
+        self.host, self.max_subs, self.max_segs = [], 1, 1
+
+
+class JpegScanBatch:
+    """What ``JpegDecoder.prepare`` returns: per geometry a ``JpegScanGroup``; ``fallback`` as in ``JpegBatch``; ``streams``:
+    the bytes of the call (the host decoder reads them for whatever the device does not take)."""
+
+    def __init__(self, n, groups, fallback, sizes, streams):
+        self.n, self.groups, self.fallback, self.sizes, self.streams = n, groups, fallback, sizes, streams
+
+    def layout(self):
+        return [(g.geometry, tuple(g.indices)) for g in self.groups]
+
+
+JpegDeviceGroup = collections.namedtuple('JpegDeviceGroup', 'geometry indices coef quant')
+JPEG_SYNC_ROUNDS = 2                                                        # (DESIGN 4.9d: twice the largest number of rounds measured)
+
+
 class JpegDecoder:
     """JPEG bytes -> (N, H, W, 3) uint8 RGB on the GPU, equal to ``PIL.Image.open(...).convert('RGB')`` byte for byte.
 
@@ -1459,11 +1489,26 @@ class JpegDecoder:
     ``workers``: host threads of the entropy decode (ctypes releases the GIL), at most ``min(16, os.cpu_count())`` by default.
     ``fallback``: a stream the entropy decoder answers with STP3_EUNSUP (progressive, CMYK, 4:1:1, ...) is decoded by Pillow on
     the host and uploaded into the same slot of the result; ``fallback=False`` raises ``JpegUnsupported`` instead.  A corrupt
-    stream (STP3_EINVAL) always raises."""
+    stream (STP3_EINVAL) always raises.
 
-    def __init__(self, workers=None, fallback=True):
+    ``entropy='device'`` decodes the Huffman scan on the GPU as well (csrc/stp3_jpeg_huff.hip): the host only strips the byte
+    stuffing and cuts the scan at its restart markers (``prepare``), the compressed scan is uploaded instead of the
+    coefficients.  The result is the same by construction: an image the device reports (a stream it calls corrupt, one whose
+    subsequences had not synchronised after ``sync_rounds`` further launches) or ``prepare`` calls irregular goes through the
+    host decoder above, which raises what it raises in host mode.  On a CPU ``device`` the mode is the host decoder.
+    ``last_stats``: per call, how many images the device decoded, the host decoder, Pillow."""
+
+    def __init__(self, workers=None, fallback=True, entropy='host', sync_rounds=JPEG_SYNC_ROUNDS):
+        if entropy not in ('host', 'device'):
+            raise ValueError("entropy must be 'host' or 'device'")
+        if not 0 <= int(sync_rounds) <= 64:
+            raise ValueError('sync_rounds must be in [0, 64]')
         self.workers = max(1, int(workers)) if workers is not None else min(16, os.cpu_count() or 1)
         self.fallback = fallback
+        self.entropy_mode, self.sync_rounds = entropy, int(sync_rounds)
+        self.last_stats = {'device': 0, 'host': 0, 'pillow': 0}
+        self.last_flags = []                                                    # per group: the (n, sync_rounds + 3) words of the call
+        self._workspace = {}
         self._pool = None
 
     # ---- host ---------------------------------------------------------------------------------------------------------
@@ -1662,6 +1707,10 @@ class JpegDecoder:
             if out is not None:
                 out.copy_(ref)
             return out if out is not None else ref
+        return self._reconstruct_staged(batch, staged, dev, stacked, out)
+
+    def _reconstruct_staged(self, batch, staged, dev, stacked, out):
+        """The launches of ``reconstruct`` on coefficients that are on the device: staged = [(group, coef, quant)]."""
         if stacked and out is None:
             out = torch.empty((batch.n,) + tuple(batch.sizes[0]) + (3,), dtype=torch.uint8, device=dev)
         images = [None] * batch.n
@@ -1683,8 +1732,170 @@ class JpegDecoder:
                 images[i] = host.to(dev)
         return out if stacked else images
 
+    # ---- entropy decode on the device -----------------------------------------------------------------------------------
+    def prepare(self, streams, out=None):
+        """Headers and stp3_jpeg_scan_prepare on the thread pool, grouped by geometry as ``entropy`` groups: a
+        ``JpegScanBatch``; ``out``: a batch of the same layout whose buffers are large enough, to refill."""
+        streams = [s if isinstance(s, bytes) else bytes(s) for s in streams]
+        lib = _lib.lib()
+
+        def header(s):
+            h = _lib.JpegHeader()
+            rc = lib.stp3_jpeg_info(s, len(s), ctypes.byref(h))
+            if rc == _lib.STP3_EUNSUP:
+                return JpegUnsupported(jpeg_unsupported_reason(s))
+            if rc != 0:
+                return _lib.Stp3HipError(f'stp3_jpeg_info failed: {_lib._ERRORS.get(rc, rc)}')
+            return h
+
+        heads, fallback = self._map(header, streams), {}
+        for i, h in enumerate(heads):
+            if isinstance(h, JpegUnsupported):
+                if not self.fallback:
+                    raise JpegUnsupported(f'image {i}: {h}') from None
+                fallback[i] = (str(h), streams[i])
+                heads[i] = None
+            elif isinstance(h, Exception):
+                raise _lib.Stp3HipError(f'image {i}: {h}') from None
+        order = {}
+        for i, h in enumerate(heads):
+            if h is not None:
+                order.setdefault(_geometry(h), []).append(i)
+        layout = [(g, tuple(idx)) for g, idx in order.items()]
+        need = [-(-max(lib.stp3_jpeg_scan_bytes(ctypes.byref(heads[i]), len(streams[i])) for i in idx) // 128) * 128 for _, idx in layout]
+        if out is not None:
+            if out.layout() != layout or out.n != len(streams) or any(g.stride < b for g, b in zip(out.groups, need)):
+                raise ValueError('the batch to refill has another layout (geometry or order of the images) or smaller scan buffers')
+            groups = out.groups
+        else:
+            groups = [JpegScanGroup(g, idx, b, torch.cuda.is_available()) for (g, idx), b in zip(layout, need)]
+        jobs = [(grp, k, i) for grp in groups for k, i in enumerate(grp.indices)]
+
+        def job(j):
+            grp, k, i = j
+            return lib.stp3_jpeg_scan_prepare(streams[i], len(streams[i]), grp.scans[k].data_ptr(), grp.stride, grp.descs[k].data_ptr(),
+                                              grp.quant[k].data_ptr())
+
+        for grp in groups:
+            grp.host = []
+        for (grp, k, i), rc in zip(jobs, self._map(job, jobs)):
+            if rc != 0:                                                         # irregular (or anything else): the host decoder's
+                grp.host.append(k)
+                grp.descs[k].zero_()
+        for grp in groups:
+            words = grp.descs.numpy().view(np.int32)
+            grp.max_subs, grp.max_segs = max(1, int(words[:, 0].max())), max(1, int(words[:, 1].max()))
+        sizes = [(h.height, h.width) if h is not None else None for h in heads]
+        for i, (_, s) in fallback.items():
+            sizes[i] = self._pillow_size(s)
+        return JpegScanBatch(len(streams), groups, fallback, sizes, streams)
+
+    def _work(self, dev, nbytes):
+        ws = self._workspace.get(dev)
+        if ws is None or ws.numel() < nbytes:
+            ws = self._workspace[dev] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        return ws
+
+    def entropy_device_launch(self, grp, scans, descs, coef, status, workspace=None):
+        """stp3_jpeg_entropy_device alone on tensors that are on the GPU: the scans and descriptors of a ``JpegScanGroup``
+        into ``coef`` (n, coef_count) int16 and ``status`` (n,) int32.  Enqueues only."""
+        g, n = grp.geometry, len(grp.indices)
+        if coef.dtype != torch.int16 or tuple(coef.shape) != (n, _coef_count(g)) or status.dtype != torch.int32 or status.numel() != n or \
+                tuple(scans.shape) != (n, grp.stride) or not all(t.is_contiguous() for t in (scans, descs, coef, status)):
+            raise ValueError('coef must be (N, coef_count) int16, status (N,) int32, scans (N, stride) uint8, all contiguous')
+        ops._need_gpu(scans, descs, coef, status)
+        d = _lib.JpegHuffDims(n, g.width, g.height, g.components, g.hs, g.vs, grp.stride, grp.max_subs, grp.max_segs)
+        nbytes = _lib.c_size_t()
+        lib = _lib.lib()
+        _lib.check(lib.stp3_jpeg_entropy_workspace_bytes(ctypes.byref(d), self.sync_rounds, ctypes.byref(nbytes)),
+                   'stp3_jpeg_entropy_workspace_bytes')
+        if workspace is None:
+            workspace = self._work(coef.device, nbytes.value)
+        _lib.check(lib.stp3_jpeg_entropy_device(ctypes.byref(d), ops._ptr(scans), ops._ptr(descs), ops._ptr(coef), ops._ptr(status),
+                                                ops._ptr(workspace), workspace.numel(), self.sync_rounds, ops._stream()),
+                   'stp3_jpeg_entropy_device')
+        return workspace
+
+    def _entropy_device(self, batch, dev, staged_quant=None):
+        """The device decode of a prepared batch: [(group, coef, quant)] on ``dev``, every image the device did not take decoded
+        by the host decoder and uploaded into its slot; one copy of the status words, one synchronise."""
+        lib = _lib.lib()
+        total = sum(len(g.indices) for g in batch.groups)
+        status = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+        staged, at, self.last_flags = [], 0, []
+        keep_flags = getattr(self, 'keep_flags', False)
+        for gi, grp in enumerate(batch.groups):
+            n = len(grp.indices)
+            quant = staged_quant[gi] if staged_quant is not None else grp.quant.to(dev, non_blocking=True)
+            scans, descs = grp.scans.to(dev, non_blocking=True), grp.descs.to(dev, non_blocking=True)
+            coef = torch.empty(n, _coef_count(grp.geometry), dtype=torch.int16, device=dev)
+            # one workspace per group while the launches of the call are in flight
+            ws = self.entropy_device_launch(grp, scans, descs, coef, status[at:at + n],
+                                            workspace=None if len(batch.groups) == 1 else self._group_workspace(grp, dev))
+            if keep_flags:
+                self.last_flags.append(ws[:n * (self.sync_rounds + 3) * 4].clone())
+            staged.append((grp, coef, quant))
+            at += n
+        codes = status.cpu().tolist()                                          # the one synchronise of the call
+        if keep_flags:
+            self.last_flags = [f.cpu().numpy().view(np.int32).reshape(-1, self.sync_rounds + 3) for f in self.last_flags]
+        at, on_host = 0, 0
+        for grp, coef, quant in staged:
+            n = len(grp.indices)
+            redo = sorted(set(grp.host) | {k for k in range(n) if codes[at + k] != 0})
+            at += n
+            if not redo:
+                continue
+            host_coef = torch.empty(len(redo), coef.shape[1], dtype=torch.int16, pin_memory=torch.cuda.is_available())
+            host_quant = torch.empty(len(redo), 3, 64, dtype=torch.int16, pin_memory=torch.cuda.is_available())
+
+            def decode(j):
+                s, h = batch.streams[grp.indices[redo[j]]], _lib.JpegHeader()
+                return lib.stp3_jpeg_entropy(s, len(s), host_coef[j].data_ptr(), host_coef.shape[1], host_quant[j].data_ptr(), ctypes.byref(h))
+
+            for j, rc in enumerate(self._map(decode, list(range(len(redo))))):
+                if rc != 0:
+                    raise _lib.Stp3HipError(f'image {grp.indices[redo[j]]}: stp3_jpeg_entropy failed: {_lib._ERRORS.get(rc, rc)}')
+            where = torch.tensor(redo, device=dev)
+            coef.index_copy_(0, where, host_coef.to(dev, non_blocking=True))
+            quant.index_copy_(0, where, host_quant.to(dev, non_blocking=True))
+            on_host += len(redo)
+        self.last_stats = {'device': total - on_host, 'host': on_host, 'pillow': len(batch.fallback)}
+        return staged
+
+    def _group_workspace(self, grp, dev):
+        g, n = grp.geometry, len(grp.indices)
+        d = _lib.JpegHuffDims(n, g.width, g.height, g.components, g.hs, g.vs, grp.stride, grp.max_subs, grp.max_segs)
+        nbytes = _lib.c_size_t()
+        _lib.check(_lib.lib().stp3_jpeg_entropy_workspace_bytes(ctypes.byref(d), self.sync_rounds, ctypes.byref(nbytes)),
+                   'stp3_jpeg_entropy_workspace_bytes')
+        return torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+
+    def entropy_device(self, streams, device):
+        """The entropy decode alone, on the device: ([JpegDeviceGroup(geometry, indices, coef, quant)], the prepared batch) -- what
+        ``entropy`` returns per group, in device memory.  Streams behind the Pillow fallback are in ``batch.fallback`` only."""
+        dev = torch.device(device)
+        batch = self.prepare(streams)
+        quants = [grp.quant.to(dev, non_blocking=True) for grp in batch.groups]
+        if quants and not quants[0].is_cuda or not quants and dev.type != 'cuda':
+            raise _lib.Stp3HipError('entropy_device needs a GPU device: there is no fallback path')
+        staged = self._entropy_device(batch, dev, quants)
+        return [JpegDeviceGroup(grp.geometry, tuple(grp.indices), coef, quant) for grp, coef, quant in staged], batch
+
     def __call__(self, streams, device, out=None):
-        return self.reconstruct(self.entropy(streams), device, out=out)
+        if self.entropy_mode == 'device':
+            dev = torch.device(device)
+            batch = self.prepare(streams)
+            quants = [grp.quant.to(dev, non_blocking=True) for grp in batch.groups]
+            if quants and quants[0].is_cuda or not quants and dev.type == 'cuda':
+                stacked = len(set(batch.sizes)) == 1
+                if out is not None and (not stacked or tuple(out.shape) != (batch.n,) + tuple(batch.sizes[0]) + (3,) or out.dtype != torch.uint8
+                                        or out.device.type != dev.type or not out.is_contiguous()):
+                    raise ValueError('out must be a contiguous uint8 tensor (N, H, W, 3) on the device of the call')
+                return self._reconstruct_staged(batch, self._entropy_device(batch, dev, quants), dev, stacked, out)
+        batch = self.entropy(streams)                                           # (a CPU device: the host decoder is the mode)
+        self.last_stats = {'device': 0, 'host': batch.n - len(batch.fallback), 'pillow': len(batch.fallback)}
+        return self.reconstruct(batch, device, out=out)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
